@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark: gossip rounds of a 65,536-node simulated ringpop cluster.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run builds the cluster, pre-rolls and warms it up, times --steps
+rounds and prints the result line (value, ms_per_step, the ping merge's
+roofline from the HIP events inside the timed region); with --dump-outputs DIR
+it also writes the cluster's state after the last timed round as DIR/*.npy
+(dump_gossip).  Everything else -- this box's ceilings and clocks, the
+per-stage pass, the rocprofv3 traffic passes, tick-cluster's observed mode,
+configs 1, 2, 3 and 5 and the CPU baselines -- runs only with --full.
 
 A step is one gossip round (every live node pings once: iterator, piggyback
 issue, receiver merge + response, sender merge) of config 4:
@@ -13,7 +21,7 @@ reference's accounting, all ranks); beside it rounds/s, the changes whose
 view cell was physically read (`touched`, after the sender and seen filters)
 and applied/s.  Inputs are resident in HBM before timing.
 
-N = 1 also runs, after the headline, config 3 (100 M string keys vs a
+N = 1 with --full also runs, after the headline, config 3 (100 M string keys vs a
 10,000-server ring: keys/s, roofline, sampled parity) and config 5 (10 %
 fail-stops + a false-suspicion storm at 65,536 nodes: rounds to converge,
 ms/round, end-state checks), reported as sub-objects of the same JSON line,
@@ -66,6 +74,12 @@ def parse(argv=None):
     p.add_argument("--nodes", type=int, default=65536)
     p.add_argument("--churn", type=int, default=None, help="alive re-assertions per round (default ceil(1%% N))")
     p.add_argument("--seed", type=int, default=2024)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what they computed as DIR/<name>.npy (float32 / float64)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline: box ceilings and clocks, the per-stage pass, "
+                        "rocprofv3 traffic, observed mode, configs 1/2/3/5, CPU baselines (each still subject to "
+                        "its --no-* option)")
     p.add_argument("--cpu-nodes", type=int, default=4096)
     p.add_argument("--cpu-seconds", type=float, default=10.0)
     p.add_argument("--no-cpu-baseline", action="store_true")
@@ -85,7 +99,12 @@ def parse(argv=None):
     p.add_argument("--storm-ppm", type=int, default=1000, help="failure: false suspicions per round, ppm of live nodes")
     p.add_argument("--storm-rounds", type=int, default=20, help="failure: rounds of the false-suspicion storm")
     p.add_argument("--max-rounds", type=int, default=400, help="failure: give up after this many rounds")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error("--steps: at least one timed step")
+    if args.dump_outputs and args.loop_ranks > 1:
+        p.error("--dump-outputs: not with --loop-ranks")
+    return args
 
 
 # ----------------------------------------------------------------- CPU baselines
@@ -361,7 +380,7 @@ def _pmc_child(args, counter, outdir):
     rounds = args.preroll + 6  # (the timed 3 rounds and the 3-round per-stage pass after them)
     cmd = [rp, "--pmc", counter, "--kernel-include-regex", regex, "-d", outdir, "-o", "run", "--output-format", "csv",
            "--", sys.executable, os.path.abspath(__file__), "--nodes", str(args.nodes), "--steps", "3", "--warmup", "0",
-           "--preroll", str(args.preroll), "--no-extras", "--no-cpu-baseline", "--no-traffic"]
+           "--preroll", str(args.preroll), "--full", "--no-extras", "--no-cpu-baseline", "--no-traffic"]
     env = dict(os.environ, TMPDIR=os.environ.get("TMPDIR", "/tmp"))
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
     if r.returncode != 0:
@@ -517,6 +536,8 @@ def run_lookup(args, with_cpu=True):
     got = own_all[idx]
     mismatches = int((got != want).sum())
     assert mismatches == 0, f"{mismatches} lookup owners differ from the oracle"
+    if args.dump_outputs:  # (the owners of the seeded sample of the batch, as the last timed lookup wrote them)
+        write_outputs(args.dump_outputs, {"key_index": idx.astype(np.float64), "owners": got.astype(np.float64)})
 
     # handleOrProxyAll's grouping (index.js:636-645) of the same batch on the
     # device: owner-sorted runs, first-appearance group order
@@ -582,7 +603,7 @@ def run_lookup(args, with_cpu=True):
                          "note": "device_ms: HIP events around rp_ring_add_remove's device work (replica hashing of "
                                  "the names copied over PCIe, 4-pass stable radix sort, dedupe, compaction, "
                                  "lookup directories); ms: host wall clock of the call; frac from device_ms"}
-    if with_cpu and not args.no_cpu_baseline:
+    if with_cpu and args.full and not args.no_cpu_baseline:
         # oracle farmhash32 (C) + numpy lower bound, one host core, on a
         # bounded sample of the same keys (strings formatted before timing)
         ks = oracle.lookup_keys(args.seed, np.arange(1_000_000))
@@ -836,6 +857,11 @@ def run_failure(args, world=1, rank=0, dist=None, sim_cls=None):
                                         "algorithmic_bytes_per_view": 16 * n}}
     if world > 1 or args.shards > 1:
         out["exchange"] = exchange_report(S.exchange_stats(), rank, world, kt, dist)
+    if getattr(args, "dump_outputs", None):  # the converged cluster, and the round it converged at (-1: it did not)
+        arrays = dump_views(S, args, lo, hi)
+        arrays["converged_at"] = np.array([-1 if converged_at is None else converged_at], dtype=np.float64)
+        if rank == 0:
+            write_outputs(args.dump_outputs, arrays)
     S.close()
     return out
 
@@ -1018,14 +1044,59 @@ def make_sim(args, n, k, world, rank, dist, sim_cls=None, failures=None, storm=N
     raise ShardBuildError("; ".join(errs)[:500])
 
 
+# ----------------------------------------------------------------- --dump-outputs
+DUMP_BYTES_MAX = 64 << 20
+DUMP_COUNTERS = ("evaluated", "applied", "full_syncs", "messages", "pings")  # (the protocol's own counts)
+
+
+def write_outputs(dirname, arrays):
+    """--dump-outputs: DIR/<name>.npy per array (float32 or float64, at most 64 MB in all)."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BYTES_MAX and all(a.dtype in (np.float32, np.float64) for a in arrays.values()), total
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def dump_views(S, args, lo, hi):
+    """What a caller reads off a cluster, for nodes lo .. hi (this process's
+    shard): every node's membership checksum and view counts (absent / alive /
+    suspect / faulty / leave / ring servers), and the whole views (status and
+    incarnation per member) of a seeded sample of the nodes."""
+    import numpy as np
+    n = S.n
+    take = max(1, min(32, hi - lo, (48 << 20) // (12 * n)))
+    nodes = np.sort(np.random.default_rng(args.seed).choice(np.arange(lo, hi), size=take, replace=False))
+    st, inc = np.zeros((take, n), dtype=np.float32), np.zeros((take, n), dtype=np.float64)
+    for i, v in enumerate(nodes):
+        s, c = S.view(int(v))
+        st[i], inc[i] = s, c  # (incarnations are millisecond stamps below 2^53)
+    return {"checksums": S.checksums()[lo:hi].astype(np.float64),
+            "view_counts": S.view_counts()[lo:hi].astype(np.float64),
+            "view_nodes": nodes.astype(np.float64), "view_status": st, "view_incarnation": inc}
+
+
+def dump_gossip(S, args, d, rank=0):
+    """The cluster as the last timed round left it (dump_views) and the
+    protocol counters summed over the timed rounds (DUMP_COUNTERS' order).
+    Every rank reads its shard (the reads may be collectives); rank 0 writes its own."""
+    import numpy as np
+    lo, hi = S.shard_range()
+    out = dump_views(S, args, lo, hi)
+    out["counters"] = np.array([d[c] for c in DUMP_COUNTERS], dtype=np.float64)
+    if rank == 0:
+        write_outputs(args.dump_outputs, out)
+
+
 # ----------------------------------------------------------------- config 4 (headline)
 def run_gossip(args, world, rank, dist, sim_cls=None):
     n = args.nodes
     k = args.churn if args.churn is not None else math.ceil(0.01 * n)
-    # this box's ceilings and clocks (the real device only; every rank measures its own GPU)
+    # --full: this box's ceilings and clocks (the real device only; every rank measures its own GPU)
     # (RP_BENCH_NO_CAL=1: skip it -- experiments on the allocation order only)
-    box = box_ceiling() if sim_cls is None and not os.environ.get("RP_BENCH_NO_CAL") else None
-    clk = ClockSampler(_pci_bus_id()) if sim_cls is None else None
+    box = box_ceiling() if args.full and sim_cls is None and not os.environ.get("RP_BENCH_NO_CAL") else None
+    clk = ClockSampler(_pci_bus_id()) if args.full and sim_cls is None else None
     S, mode, _ = make_sim(args, n, k, world, rank, dist, sim_cls=sim_cls)
     # pre-roll to the steady state the line is quoted on (the log fill of a
     # node takes ~50 rounds to stop growing), then the warmup rounds
@@ -1040,9 +1111,9 @@ def run_gossip(args, world, rank, dist, sim_cls=None):
 
     # Only the line's roofline stage (the ping merge) carries HIP events inside
     # the timed region -- two per stage launch on the simulation stream, ~0.1
-    # ms per round when every stage has them -- and a second pass of the same
-    # length right after times every stage (and the exchange steps) for the
-    # per-stage breakdown and the exchange report.
+    # ms per round when every stage has them -- and with --full a second pass
+    # of the same length right after times every stage (and the exchange
+    # steps) for the per-stage breakdown and the exchange report.
     S.enable_timing(True, stages=["merge_ping"])
     barrier()
     if clk:
@@ -1059,13 +1130,17 @@ def run_gossip(args, world, rank, dist, sim_cls=None):
     kt_timed = S.kernel_times()
     d = {key: c1[key] - c0[key] for key in c1}
     dl_timed = {key: l1[key] - l0[key] for key in l1}
-    S.enable_timing(True)
-    S.run(args.steps, churn=True)
-    S.sync()
-    l2 = S.local_counters()
-    kt = S.kernel_times()
+    if args.dump_outputs:
+        dump_gossip(S, args, d, rank)
+    kt, dl = kt_timed, None
+    if args.full:  # the per-stage pass
+        S.enable_timing(True)
+        S.run(args.steps, churn=True)
+        S.sync()
+        l2 = S.local_counters()
+        kt = S.kernel_times()
+        dl = {key: l2[key] - l1[key] for key in l2}
     xs = S.exchange_stats()
-    dl = {key: l2[key] - l1[key] for key in l2}
 
     # (the sharded counters are cluster-wide already: no sum over ranks)
     tot = {key: float(d[key]) for key in ("evaluated", "applied", "touched")}
@@ -1079,7 +1154,7 @@ def run_gossip(args, world, rank, dist, sim_cls=None):
     xrep = exchange_report(xs, rank, world, kt, dist) if (world > 1 or args.shards > 1) else None
 
     observed = None
-    if world == 1 and args.shards <= 1 and not args.no_extras:
+    if args.full and world == 1 and args.shards <= 1 and not args.no_extras:
         # tick-cluster's convergence check (scripts/tick-cluster.js:88-115):
         # every live node's membership checksum read after every round.  The
         # device computes farmhash checksums when read; here all
@@ -1141,27 +1216,30 @@ def run_gossip(args, world, rank, dist, sim_cls=None):
                         "exceed the bytes moved"}
         return o
 
-    stages = {
-        "ping_merge": stage("merge_ping", dl["touched_ping_merge"], dl["applied_ping_merge"], dl["scanned_recv_issue"],
-                            dl["written_recv_issue"], dl["eval_ping_merge"],
-                            "k_phase2 stage (k_p2_lists, k_p2_apply x2, k_p2_respond x2, k_phase2)"),
-        "resp_merge": stage("merge_resp", dl["touched"] - dl["touched_ping_merge"], dl["applied_resp_merge"], 0, 0,
-                            dl["eval_resp_merge"], "k_phase3"),
-        "send_issue": stage("issue", 0, 0, dl["scanned_send_issue"], dl["written_send_issue"], None,
-                            "issue stage (k_iterate, k_shuffle, k_phase1)"),
-    }
-    # the line's roofline: the stage with the most device time (the ping merge in steady state)
-    name = max(stages, key=lambda c: stages[c]["avg_launch_ms"] * stages[c]["launches"])
-    roofline = dict(stages[name])
+    # the ping merge's launches timed inside the timed region itself (the only stage with events there)
+    name = "ping_merge"
+    roofline = stage("merge_ping", dl_timed["touched_ping_merge"], dl_timed["applied_ping_merge"],
+                     dl_timed["scanned_recv_issue"], dl_timed["written_recv_issue"], dl_timed["eval_ping_merge"],
+                     "k_phase2 stage (k_p2_lists, k_p2_apply x2, k_p2_respond x2, k_phase2)", kt=kt_timed)
+    roofline["timing"] = ("HIP events around this stage's launches on the simulation stream, inside the "
+                          "timed region; the other stages and kernel_ms from a second pass of --steps rounds"
+                          + ("" if dl else " (--full)"))
+    stages = None
+    if dl:  # (--full: the per-stage pass ran)
+        stages = {
+            "ping_merge": stage("merge_ping", dl["touched_ping_merge"], dl["applied_ping_merge"],
+                                dl["scanned_recv_issue"], dl["written_recv_issue"], dl["eval_ping_merge"],
+                                "k_phase2 stage (k_p2_lists, k_p2_apply x2, k_p2_respond x2, k_phase2)"),
+            "resp_merge": stage("merge_resp", dl["touched"] - dl["touched_ping_merge"], dl["applied_resp_merge"], 0, 0,
+                                dl["eval_resp_merge"], "k_phase3"),
+            "send_issue": stage("issue", 0, 0, dl["scanned_send_issue"], dl["written_send_issue"], None,
+                                "issue stage (k_iterate, k_shuffle, k_phase1)"),
+        }
+        # the line's roofline: the stage with the most device time (the ping merge in steady state)
+        name = max(stages, key=lambda c: stages[c]["avg_launch_ms"] * stages[c]["launches"])
+        if name != "ping_merge":
+            roofline = dict(stages[name])
     roofline["stage"] = name
-    if name == "ping_merge":
-        # its launches timed inside the timed region itself (the only stage with events there)
-        roofline = stage("merge_ping", dl_timed["touched_ping_merge"], dl_timed["applied_ping_merge"],
-                         dl_timed["scanned_recv_issue"], dl_timed["written_recv_issue"], dl_timed["eval_ping_merge"],
-                         "k_phase2 stage (k_p2_lists, k_p2_apply x2, k_p2_respond x2, k_phase2)", kt=kt_timed)
-        roofline["stage"] = name
-        roofline["timing"] = ("HIP events around this stage's launches on the simulation stream, inside the "
-                              "timed region; the other stages and kernel_ms from a second pass of --steps rounds")
     if box:
         for st in stages.values():
             st["frac_of_box"] = frac_of_box(st, box)
@@ -1197,8 +1275,9 @@ def run_gossip(args, world, rank, dist, sim_cls=None):
         "evaluated_per_round": round(tot["evaluated"] / args.steps, 1),
         "kernel_ms": {c: round(v[0], 3) for c, v in kt.items()},
         "roofline": roofline,
-        "stages": stages,
     }
+    if stages:
+        out["stages"] = stages
     if box:
         out["box_ceiling"] = box
     if clk:
@@ -1312,8 +1391,8 @@ def main(argv=None, sim_cls=None):
         print(json.dumps(run_lookup(args)), flush=True)
         return 0
     traffic = None
-    if (world == 1 and args.shards <= 1 and args.loop_ranks <= 1 and args.workload == "gossip" and sim_cls is None
-            and not args.no_traffic):
+    if (args.full and world == 1 and args.shards <= 1 and args.loop_ranks <= 1 and args.workload == "gossip"
+            and sim_cls is None and not args.no_traffic):
         # (child runs under rocprofv3 before this process touches the GPU:
         # two 65,536-node clusters do not fit in HBM together)
         try:
@@ -1367,11 +1446,11 @@ def main(argv=None, sim_cls=None):
         return 3
     if out is not None and traffic is not None:
         attach_traffic(out, traffic)
-    if out is not None and world == 1 and args.shards <= 1:
+    if out is not None and args.full and world == 1 and args.shards <= 1:
         if not args.no_extras:
             # configs 3 and 5 on the same GPU, after the headline cluster is freed
             sub = argparse.Namespace(**vars(args))
-            sub.steps, sub.warmup = 10, 2
+            sub.steps, sub.warmup, sub.dump_outputs = 10, 2, None  # (--dump-outputs is the headline's)
             lk = run_lookup(sub, with_cpu=not args.no_cpu_baseline)
             out["config3"] = _sub(lk, ("metric", "value", "unit", "ms_per_step", "config", "roofline", "parity",
                                        "group_by_owner", "ring_build", "cpu_baseline"))
@@ -1391,7 +1470,7 @@ def main(argv=None, sim_cls=None):
                 out["config3"]["roofline"]["pmc_error"] = lp.get("error")
             out["config2"] = run_config2(args)
             out["config1"] = run_config1(args)
-            fl = run_failure(args)
+            fl = run_failure(sub)  # (reads neither --steps nor --warmup)
             out["config5"] = _sub(fl, ("metric", "value", "unit", "steps", "ms_per_step",
                                        "ms_per_step_with_stage_events", "config",
                                        "first_agreement_round", "member_updates_per_s", "full_syncs", "end_state",

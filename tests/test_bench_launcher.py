@@ -11,6 +11,7 @@ import subprocess
 import sys
 import types
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -133,8 +134,8 @@ def test_visible_gpus_does_not_start_hip():
 
 def test_single_gpu_times_only_the_ping_merge_inside_the_timed_region():
     """One process: the timed rounds carry HIP events for the roofline stage
-    only; a second pass of --steps rounds times every stage for the breakdown."""
-    args = bench.parse(["--steps", "3", "--warmup", "1", "--preroll", "2", "--nodes", "64", "--no-extras",
+    only; with --full a second pass of --steps rounds times every stage for the breakdown."""
+    args = bench.parse(["--steps", "3", "--warmup", "1", "--preroll", "2", "--nodes", "64", "--full", "--no-extras",
                         "--no-cpu-baseline", "--no-traffic"])
     made = []
 
@@ -150,3 +151,68 @@ def test_single_gpu_times_only_the_ping_merge_inside_the_timed_region():
     assert S.r == 2 + 1 + 3 + 3  # pre-roll + warmup, the timed rounds, the per-stage pass
     assert out["roofline"]["stage"] == "ping_merge" and "timing" in out["roofline"]
     assert out["ms_per_step"] >= 0 and out["steps"] == 3
+    assert set(out["stages"]) == {"ping_merge", "resp_merge", "send_issue"}
+
+
+class DumpSim(FakeGossipSim):
+    """FakeGossipSim with the reads --dump-outputs makes; `made` collects the instances."""
+    made = []
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        DumpSim.made.append(self)
+
+    def counters(self):
+        return dict(super().counters(), full_syncs=2 * self.r, messages=7 * self.r, pings=3 * self.r)
+
+    def shard_range(self):
+        return 0, self.n
+
+    def checksums(self):
+        self.log.append(("read", self.r))
+        return np.arange(self.n, dtype=np.uint32) * 65537 + self.r
+
+    def view_counts(self):
+        return np.full((self.n, 6), self.r, dtype=np.uint32)
+
+    def view(self, v):
+        return np.full(self.n, v % 5, dtype=np.uint8), np.full(self.n, 1500000000000 + v, dtype=np.uint64)
+
+
+def test_plain_run_times_the_steps_and_nothing_else(tmp_path):
+    """Without --full: pre-roll, warmup and the --steps timed rounds only (no
+    per-stage pass, no stages, ceilings, clocks, extras or baselines in the
+    line); --dump-outputs reads the cluster right after the last timed round
+    and writes float32 / float64 arrays, the same from run to run."""
+    dumps = []
+    for d in ("a", "b"):
+        DumpSim.made.clear()
+        args = bench.parse(["--gpus", "1", "--steps", "4", "--warmup", "1", "--preroll", "2", "--nodes", "64",
+                            "--dump-outputs", str(tmp_path / d)])
+        out = bench.run_gossip(args, 1, 0, None, sim_cls=DumpSim)
+        (S,) = DumpSim.made
+        assert S.r == 2 + 1 + 4
+        assert S.log == [("timing", True, ["merge_ping"]), ("read", 2 + 1 + 4)]
+        assert out["steps"] == 4 and out["ms_per_step"] >= 0 and out["roofline"]["stage"] == "ping_merge"
+        for key in ("stages", "box_ceiling", "clocks", "observed_checksums", "config3", "config5", "cpu_baseline"):
+            assert key not in out, key
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype"):
+            assert key in out, key
+        dumps.append({f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = dumps
+    assert set(a) == {"checksums", "view_counts", "view_nodes", "view_status", "view_incarnation", "counters"}
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        assert np.array_equal(a[name], b[name]), name
+    assert a["checksums"].tolist() == [i * 65537 + 7 for i in range(64)]
+    assert a["counters"].tolist() == [4000.0, 40.0, 8.0, 28.0, 12.0]  # the 4 timed rounds' own counts
+    nodes = a["view_nodes"].astype(int)
+    assert len(nodes) == 32 and len(set(nodes)) == 32 and a["view_status"].shape == (32, 64)
+    assert a["view_incarnation"][:, 0].tolist() == [1500000000000 + v for v in nodes]  # exact in float64
+
+
+def test_steps_sets_the_number_of_timed_steps():
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    assert bench.parse([]).full is False and bench.parse(["--full"]).full is True

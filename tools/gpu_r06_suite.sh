@@ -12,10 +12,11 @@ if [ "${2:-}" != skip-tests ]; then
   rc=$?; echo "pytest rc=$rc"; tail -3 gpurun_out/pytest_$TAG.log
   [ $rc -eq 0 ] || exit $rc
 fi
-timeout -k 10 900 python -u bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err
-rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || { tail -5 gpurun_out/bench_$TAG.err; exit $rc; }
+OUT=${BENCH_OUT:-bench_out}; mkdir -p "$OUT"  # (the default line, every section: --full)
+timeout -k 10 900 python -u bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || { tail -5 $OUT/bench_$TAG.err; exit $rc; }
 python3 -c "
-import json; d = json.loads(open('gpurun_out/bench_$TAG.json').read().strip().splitlines()[-1])
+import json; d = json.loads(open('$OUT/bench_$TAG.json').read().strip().splitlines()[-1])
 print('ms/round', d['ms_per_step'], 'frac', d['roofline']['frac'], 'box', d.get('box_ceiling'), 'clk', d.get('clocks'))
 print('c5', d.get('config5', {}).get('ms_per_step'), 'obs', d.get('observed_checksums', {}).get('checksums_ms'))
 "

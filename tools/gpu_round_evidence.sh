@@ -12,8 +12,9 @@ export TMPDIR=/tmp
 fatal() { [ "$1" -eq 124 ] || [ "$1" -eq 137 ] || [ "$1" -eq 134 ] || [ "$1" -eq 139 ]; }
 timeout -k 10 900 python -u -m pytest tests -q --timeout 300 --timeout-method thread -m gpu "$@" > gpurun_out/pytest_gpu_$TAG.log 2>&1
 rc=$?; echo "pytest exit $rc"; tail -5 gpurun_out/pytest_gpu_$TAG.log; fatal $rc && exit $rc
-timeout -k 10 500 python -u bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err
-rc=$?; echo "bench exit $rc"; cat gpurun_out/bench_$TAG.json; [ $rc -eq 0 ] || { tail -5 gpurun_out/bench_$TAG.err; exit $rc; }
+OUT=${BENCH_OUT:-bench_out}; mkdir -p "$OUT"  # (the default line, every section: --full)
+timeout -k 10 500 python -u bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+rc=$?; echo "bench exit $rc"; cat $OUT/bench_$TAG.json; [ $rc -eq 0 ] || { tail -5 $OUT/bench_$TAG.err; exit $rc; }
 [ "${NO_PROFILE:-0}" = 1 ] && exit 0
 PROFILE_PMC=0 bash tools/profile.sh 65536 20 5 $TAG || exit $?
 bash tools/traffic.sh 65536 20 5 $TAG || exit $?
