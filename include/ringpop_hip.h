@@ -352,6 +352,55 @@ int rp_sim_node_info(rp_sim *sim, uint32_t node, int64_t *info8);
 /* ring.lookup in one node's view, for precomputed key hashes */
 int rp_sim_ring_lookup(rp_sim *sim, uint32_t node, const uint32_t *key_hashes, size_t n, int32_t *owners);
 int rp_sim_address(rp_sim *sim, uint32_t node, char *buf, size_t cap);
+
+/* ---- Request routing across the cluster (between rounds) ---------------------
+ * rp_sim_ring_checksums: HashRing.checksum of every node's ring (lib/ring.js:
+ * 96-105): farmhash32 of its servers' addresses, sorted and joined by ';'
+ * (node ids are in address sort order).  out holds cap >= n entries; a
+ * fail-stopped node reports its frozen ring, nodes of other processes' shards
+ * report 0.  Computed on the device, one wave per view, and cached until a
+ * call that can change a ring (round / run, update, handle_ping, set_views,
+ * join, load_addresses).
+ *
+ * rp_sim_route: what RingPop.handleOrProxy (index.js:607-634; lookup :409-423)
+ * and the request proxy see for a batch of requests, request i entering the cluster
+ * at node entries[i] with farmhash32(key) = key_hashes[i].  Like the wire
+ * bridge it runs with the clock of the next round: after k rounds the
+ * partition window is tested with round k.  The first rule that applies:
+ *   4 ENTRY_DEAD        the entry node is fail-stopped; dest -1
+ *   0 LOCAL             dest = HashRing.lookup(key) in the entry's ring
+ *                       (lib/ring.js:138-147) is the entry itself, or its ring
+ *                       is empty (lookup falls back to whoami); dest = entry
+ *   3 UNREACHABLE       dest is fail-stopped or the partition separates the
+ *                       two: a transport error, the reference would enter
+ *                       scheduleRetry (lib/request-proxy/send.js:105-127)
+ *   2 CHECKSUMS_DIFFER  the two nodes' ring checksums differ
+ *                       (lib/request-proxy/index.js:172-187)
+ *   1 DELIVERED         otherwise
+ * owner_agrees[i] = 1 for outcomes 1 and 2 when the lookup of the key in the
+ * destination's ring is the destination itself, else 0 (such a request counts
+ * in `misrouted`; for the other outcomes it is 0).  dests, outcomes and
+ * owner_agrees may each be NULL; stats->requests is the sum of the five
+ * outcome counts.  Retries are not modelled: a caller models send.js's
+ * schedule (:267-294) by routing the failed subset again after more rounds.
+ *
+ * rp_sim_route_uniform: the same for `count` requests generated on the
+ * device, only the statistics returned.  Request i (0-based) is
+ *   r = splitmix64_finalise(seed + (i + 1) * 0x9E3779B97F4A7C15)   (mod 2^64)
+ *   entry = ((r >> 32) * n) >> 32,   key_hash = (uint32_t)r
+ * with the finaliser z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27;
+ * z *= 0x94D049BB133111EB; z ^= z >> 31.
+ *
+ * Both need every node's view on this process's device: on one rank of a
+ * multi-process or loop cluster they return RP_ERR_UNSUPPORTED. */
+typedef struct {
+    uint64_t requests, local, delivered, checksums_differ, unreachable, entry_dead, misrouted, reserved;
+} rp_route_stats;
+int rp_sim_ring_checksums(rp_sim *sim, uint32_t *out, size_t cap);
+int rp_sim_route(rp_sim *sim, const uint32_t *entries, const uint32_t *key_hashes, size_t n, int32_t *dests,
+                 uint8_t *outcomes, uint8_t *owner_agrees, rp_route_stats *stats);
+int rp_sim_route_uniform(rp_sim *sim, uint64_t seed, uint64_t count, rp_route_stats *stats);
+
 /* per-kernel device time (HIP events on the simulation stream), ms, summed
  * since enable; names: churn, issue(phase1), merge_ping(phase2),
  * merge_resp(phase3), checksum, other */

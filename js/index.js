@@ -592,6 +592,15 @@ SimCluster.prototype.runAsync = function runAsync(k, churn) {
     });
 };
 SimCluster.prototype.checksums = function checksums() { return addon.simChecksums(this._sim, this.n); };
+// HashRing.checksum of every instance's ring (lib/ring.js:96-105), a Uint32Array
+SimCluster.prototype.ringChecksums = function ringChecksums() { return addon.simRingChecksums(this._sim); };
+// handleOrProxy for request i entering at instance entries[i] with key hash
+// keyHashes[i] (Uint32Arrays), with the next round's clock (rp_sim_route):
+// {dests, outcomes, ownerAgrees, stats}; outcomes index SimCluster.ROUTE_OUTCOMES
+SimCluster.ROUTE_OUTCOMES = ['local', 'delivered', 'checksumsDiffer', 'unreachable', 'entryDead'];
+SimCluster.prototype.route = function route(entries, keyHashes) {
+    return addon.simRoute(this._sim, entries, keyHashes);
+};
 SimCluster.prototype.addresses = function addresses() {
     if (!this._addr) {
         this._addr = [];

@@ -157,6 +157,16 @@ static bool is_typed(napi_env env, napi_value v) {
     return is_ta;
 }
 
+static bool is_u32(napi_env env, napi_value v) {
+    napi_typedarray_type t;
+    void *data;
+    napi_value ab;
+    size_t off, len = 0;
+    if (!is_typed(env, v)) return false;
+    napi_get_typedarray_info(env, v, &t, &len, &data, &ab, &off);
+    return t == napi_uint32_array;
+}
+
 /* ringAddRemove(ring, add[], remove[], addHashes?, rmHashes?, replicaPoints) -> changed */
 static napi_value js_ring_add_remove(napi_env env, napi_callback_info info) {
     size_t argc = 6;
@@ -514,6 +524,61 @@ static napi_value js_sim_checksums(napi_env env, napi_callback_info info) {
     napi_value ta = typed(env, napi_uint32_array, (size_t)n, 4, &out);
     CHECK_RP(rp_sim_read_checksums(sim, (uint32_t *)out, n));
     return ta;
+}
+
+/* simRingChecksums(sim) -> Uint32Array: HashRing.checksum of every node's ring */
+static napi_value js_sim_ring_checksums(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1];
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    rp_sim *sim;
+    uint32_t n;
+    CHECK_RP(sim_size(env, argv[0], &sim, &n));
+    void *out;
+    napi_value ta = typed(env, napi_uint32_array, (size_t)n, 4, &out);
+    CHECK_RP(rp_sim_ring_checksums(sim, (uint32_t *)out, n));
+    return ta;
+}
+
+/* simRoute(sim, Uint32Array entries, Uint32Array keyHashes) -> {dests: Int32Array,
+ * outcomes: Uint8Array, ownerAgrees: Uint8Array, stats: {...}} (rp_sim_route) */
+static napi_value js_sim_route(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3], o, so;
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    rp_sim *sim = (rp_sim *)get_external(env, argv[0]);
+    size_t ne = 0, nh = 0;
+    const uint32_t *e = argc > 1 ? opt_u32(env, argv[1], &ne) : NULL;
+    const uint32_t *h = argc > 2 ? opt_u32(env, argv[2], &nh) : NULL;
+    if (argc < 3 || !is_u32(env, argv[1]) || !is_u32(env, argv[2])) {
+        napi_throw_type_error(env, NULL, "entries and key hashes must be Uint32Arrays");
+        return NULL;
+    }
+    if (ne != nh) {
+        napi_throw_range_error(env, NULL, "entries and key hashes must have one length");
+        return NULL;
+    }
+    void *d, *oc, *ag;
+    napi_value da = typed(env, napi_int32_array, ne, 4, &d);
+    napi_value oa = typed(env, napi_uint8_array, ne, 1, &oc);
+    napi_value aa = typed(env, napi_uint8_array, ne, 1, &ag);
+    rp_route_stats st;
+    memset(&st, 0, sizeof st);
+    CHECK_RP(rp_sim_route(sim, e, h, ne, (int32_t *)d, (uint8_t *)oc, (uint8_t *)ag, &st));
+    napi_create_object(env, &so);
+    napi_set_named_property(env, so, "requests", num(env, (double)st.requests));
+    napi_set_named_property(env, so, "local", num(env, (double)st.local));
+    napi_set_named_property(env, so, "delivered", num(env, (double)st.delivered));
+    napi_set_named_property(env, so, "checksumsDiffer", num(env, (double)st.checksums_differ));
+    napi_set_named_property(env, so, "unreachable", num(env, (double)st.unreachable));
+    napi_set_named_property(env, so, "entryDead", num(env, (double)st.entry_dead));
+    napi_set_named_property(env, so, "misrouted", num(env, (double)st.misrouted));
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "dests", da);
+    napi_set_named_property(env, o, "outcomes", oa);
+    napi_set_named_property(env, o, "ownerAgrees", aa);
+    napi_set_named_property(env, o, "stats", so);
+    return o;
 }
 
 /* simView(sim, n, node) -> {status: Uint8Array, inc: Float64Array} */
@@ -1157,6 +1222,8 @@ static napi_value init(napi_env env, napi_value exports) {
     EXPORT("simFail", js_sim_fail);
     EXPORT("simPartition", js_sim_partition);
     EXPORT("simChecksums", js_sim_checksums);
+    EXPORT("simRingChecksums", js_sim_ring_checksums);
+    EXPORT("simRoute", js_sim_route);
     EXPORT("simView", js_sim_view);
     EXPORT("simMembers", js_sim_members);
     EXPORT("simChanges", js_sim_changes);

@@ -39,6 +39,15 @@ class RoundStats(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class RouteStats(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint64) for k in
+                ("requests", "local", "delivered", "checksums_differ", "unreachable", "entry_dead", "misrouted",
+                 "reserved")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
 # (name, argtypes) of every entry point declared in include/ringpop_hip.h
 _P = ctypes.c_void_p
 _U8P = ctypes.POINTER(ctypes.c_uint8)
@@ -122,6 +131,9 @@ SIGNATURES = {
     "rp_sim_node_info": ([_P, ctypes.c_uint32, _P], ctypes.c_int),
     "rp_sim_ring_lookup": ([_P, ctypes.c_uint32, _P, _SZ, _P], ctypes.c_int),
     "rp_sim_address": ([_P, ctypes.c_uint32, ctypes.c_char_p, _SZ], ctypes.c_int),
+    "rp_sim_ring_checksums": ([_P, _P, _SZ], ctypes.c_int),
+    "rp_sim_route": ([_P, _P, _P, _SZ, _P, _P, _P, ctypes.POINTER(RouteStats)], ctypes.c_int),
+    "rp_sim_route_uniform": ([_P, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(RouteStats)], ctypes.c_int),
     "rp_sim_ping_body": ([_P, ctypes.c_uint32, _P, ctypes.c_uint32, _U32P, _U32P, ctypes.POINTER(ctypes.c_uint64)],
                          ctypes.c_int),
     "rp_sim_handle_ping": ([_P, ctypes.c_uint32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint32, _P, ctypes.c_uint32,

@@ -3,7 +3,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import RoundStats, SimConfig, check, lib, ptr
+from ._lib import RoundStats, RouteStats, SimConfig, check, lib, ptr
 
 KERNEL_CATEGORIES = ("churn", "issue", "merge_ping", "merge_resp", "checksum", "other")
 STATUS_NAMES = {0: None, 1: "alive", 2: "suspect", 3: "faulty", 4: "leave"}
@@ -226,6 +226,39 @@ class Sim:
         out = np.zeros(len(h), dtype=np.int32)
         check(lib().rp_sim_ring_lookup(self._h, v, ptr(h), len(h), ptr(out)))
         return out
+
+    # ---- request routing between rounds (rp_sim_ring_checksums / rp_sim_route)
+    ROUTE_OUTCOMES = ("local", "delivered", "checksums_differ", "unreachable", "entry_dead")
+
+    def ring_checksums(self):
+        """HashRing.checksum of every node's ring (lib/ring.js:96-105); nodes
+        held by other processes are 0."""
+        out = np.zeros(self.n, dtype=np.uint32)
+        check(lib().rp_sim_ring_checksums(self._h, ptr(out), len(out)))
+        return out
+
+    def route(self, entries, key_hashes):
+        """handleOrProxy for request i entering at node entries[i] with key hash
+        key_hashes[i], with the next round's clock: (dests, outcomes (indices
+        into ROUTE_OUTCOMES), owner_agrees, stats dict)."""
+        e = np.ascontiguousarray(entries, dtype=np.uint32)
+        h = np.ascontiguousarray(key_hashes, dtype=np.uint32)
+        if e.ndim != 1 or e.shape != h.shape:
+            raise ValueError("route: two arrays of one length")
+        dests = np.zeros(len(e), dtype=np.int32)
+        outcomes = np.zeros(len(e), dtype=np.uint8)
+        agrees = np.zeros(len(e), dtype=np.uint8)
+        st = RouteStats()
+        check(lib().rp_sim_route(self._h, ptr(e), ptr(h), len(e), ptr(dests), ptr(outcomes), ptr(agrees),
+                                 ctypes.byref(st)))
+        return dests, outcomes, agrees, st.as_dict()
+
+    def route_uniform(self, seed, count):
+        """The stats of route() for `count` requests drawn on the device from
+        splitmix64(seed) (rp_sim_route_uniform)."""
+        st = RouteStats()
+        check(lib().rp_sim_route_uniform(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(count), ctypes.byref(st)))
+        return st.as_dict()
 
     def address(self, v):
         buf = ctypes.create_string_buffer(64)
