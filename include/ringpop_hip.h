@@ -166,6 +166,9 @@ typedef struct {
     uint32_t ck_lane_min;     /* a list of at least this many distinct views to checksum is hashed one view per
                                  lane (k_checksums_lanes), shorter ones one view per wave (0 = auto: 12288;
                                  1 = always per lane, 0xFFFFFFFF = never); same checksums either way */
+    uint32_t issue_wave;      /* the issue kernels of runs without faults on n % 64 == 0 nodes: 1 = one 256-thread
+                                 block per node, 2 = one wave per node in one pass, 0 = the build's default (2);
+                                 every other run takes the block kernels; same results either way */
 } rp_sim_config;
 
 typedef struct {

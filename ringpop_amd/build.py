@@ -43,14 +43,16 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-Wall", "-Wno-
 #  alt  -- every tuning constant that selects a code path set off its default
 #          (unrolls, stash size, keys per thread, ping-rank split, checksum
 #          render and side stream, compaction thresholds, seen-mask groups,
-#          the ring's 16-bit directory and incremental path), so that the
+#          the ring's 16-bit directory and incremental path, the block issue
+#          kernels where the default takes the one-wave ones), so that the
 #          parity suite runs the non-default paths too
 #          (tests/test_gpu_alt_build.py).  None of them changes a result.
 VARIANTS = {
     "diag": ["-DRP_DIAG"],
     "alt": ["-DRP_ISSUE_UNR_P1=4", "-DRP_ISSUE_UNR=4", "-DRP_ISSUE_STASH=64", "-DRP_ISSUE_P2U=1", "-DRP_SETTLED_PF=0",
             "-DRP_KPT=2", "-DRP_P2_SPLIT=1", "-DRP_CKP_SHARED=0", "-DRP_CK_SIDE=0", "-DRP_SEEN_GROUP_LOG=1",
-            "-DRP_COMPACT_MUL=2u", "-DRP_COMPACT_ADD=1024u", "-DRP_LOOKUP_DIR16=0", "-DRP_RING_INCR_MAX_POINTS=0"],
+            "-DRP_COMPACT_MUL=2u", "-DRP_COMPACT_ADD=1024u", "-DRP_LOOKUP_DIR16=0", "-DRP_RING_INCR_MAX_POINTS=0",
+            "-DRP_ISSUE_WAVE=0"],
 }
 
 

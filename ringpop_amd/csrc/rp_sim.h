@@ -261,6 +261,7 @@ enum {
     STAT_SAME_VIEW,     // issues to a destination with an identical view (wg_issue: its own entry only)
     // diagnostics (RP_DIAG builds only): shader-clock cycles by code section
     STAT_DIAG0, STAT_DIAG1, STAT_DIAG2, STAT_DIAG3, STAT_DIAG4, STAT_DIAG5,
+    STAT_WAVE_ISSUES,   // issues taken by the one-wave kernels (wave_issue; the rest: wg_issue)
     STAT_NSTATS
 };
 

@@ -22,7 +22,8 @@
 // evaluated 256 changes at a time (all changes of a batch carry distinct
 // addresses, so they are independent), and order-dependent side effects
 // (dissemination key order, ring insert order) are resolved with block-wide
-// ballot/prefix ranks in batch order.
+// ballot/prefix ranks in batch order.  (The issues of runs without faults
+// take one wave per node instead: wave_issue)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1748,6 +1749,452 @@ __device__ uint32_t wg_issue(const SimDev& S, uint32_t v, bool filter, uint32_t 
     return emitted;
 }
 
+// ---------------------------------------------------------------- issue, one wave per node
+// Dissemination.issueAs by ONE wave in ONE pass: the decisions
+// of wg_issue<FAST, !SET> with a staged seen window on 64-aligned rows
+// (n % 64 == 0), for 64-thread workgroups.  wg_issue's second pass exists
+// because four waves share one output list: a group's output base depends on
+// groups another wave scanned.  A wave that walks the groups in order knows
+// the base as a running count, so the written entries leave in the scan
+// itself -- no masks, scans, stash per wave or reductions through LDS, and no
+// workgroup barrier anywhere.  Log positions after the issue (expiries, prefix
+// packing, compaction) are wg_issue's for the same inputs.
+#ifndef RP_ISSUE_WAVE
+#define RP_ISSUE_WAVE 1  // the default of rp_sim_config.issue_wave: 1 = wave kernels where eligible, 0 = block kernels
+#endif
+#ifndef RP_WAVE_UNR
+#define RP_WAVE_UNR 8  // wave_issue: groups in flight
+#endif
+#ifndef RP_WAVE_WAVES
+#define RP_WAVE_WAVES 7  // waves per SIMD the wave kernels are compiled for (their LDS allows 30 issues per CU)
+#endif
+constexpr uint32_t WAVE_PEND = 128;  // pending written entries: a ring of two waves' worth
+struct WaveShared {
+    alignas(16) uint32_t seen[SEEN_STAGE_WORDS];  // the destination's seen bitset
+    // prefix packing: the positions (relative to the first group's) of the live
+    // entries of the window's first groups, in order, while they number at
+    // most PREFIX_CAP -- all wg_pack_prefix derives from its 512 group masks
+    uint16_t plist[PREFIX_CAP];
+    // written entries waiting to be stored 64 at a time (their side rows or
+    // origins are then read in one round trip, not one per group)
+    uint32_t pw[WAVE_PEND];  // the log word
+    uint16_t ps[WAVE_PEND];  // its slot in the row
+};
+static_assert(sizeof(WaveShared) * 16 <= 160 * 1024, "at least 16 one-wave issues per CU");
+static_assert(ISSUE_SEG * 64 <= 0x10000, "WaveShared::plist: 16-bit positions");
+// This wave's earlier global stores (buffer or flat) have completed before its
+// later loads of the same addresses issue.
+__device__ inline void wave_sync() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }
+
+// wg_compact by one wave: the same final positions (live entries in order from
+// the head); chunks of COMPACT_CK * 64 entries, each loaded whole before any
+// of it is written.
+__device__ void wave_compact(const SimDev& S, uint32_t v, uint32_t head, uint32_t tail) {
+    constexpr int CK = COMPACT_CK;
+    const size_t base = S.row(v);
+    uint32_t* const lrow = S.dko + base;
+    uint64_t* const lvrow = S.dvs + base;
+    uint32_t* const larow = S.dad + base;
+    VEnt* const vrow = S.view + base;
+    const uint32_t n = S.n;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t below = (1ull << lane) - 1ull;
+    uint32_t out = head;  // next output position (uniform)
+    for (uint32_t p0 = head; p0 - head < tail - head; p0 += CK * 64) {
+        uint32_t ko[CK], ad[CK], rk[CK];
+        uint64_t vs[CK];
+#pragma unroll
+        for (int k = 0; k < CK; k++) {
+            const uint32_t p = p0 + k * 64 + lane;
+            ko[k] = p - head < tail - head ? lrow[p % n] : TOMB_WORD;
+        }
+        uint32_t tot = 0;
+#pragma unroll
+        for (int k = 0; k < CK; k++) {
+            const uint32_t p = p0 + k * 64 + lane;
+            const bool live = !is_tomb(ko[k]);
+            vs[k] = 0;
+            ad[k] = 0;
+            if (live) ad[k] = entry_addr(S, ko[k], larow, p % n);
+            if (live && !(ko[k] & LOG_ALIVE)) vs[k] = lvrow[p % n];
+            const uint64_t m = __ballot(live);
+            rk[k] = live ? out + tot + (uint32_t)__popcll(m & below) : NONE;
+            tot += (uint32_t)__popcll(m);
+        }
+        wave_sync();  // (every source of the chunk is in registers)
+#pragma unroll
+        for (int k = 0; k < CK; k++) {
+            const uint32_t q = rk[k], i = q % n;
+            if (q == NONE || q == p0 + k * 64 + lane) continue;  // (dead, or not moving)
+            lrow[i] = ko[k];
+            if (!(ko[k] & LOG_ALIVE)) { lvrow[i] = vs[k]; larow[i] = ad[k]; }
+            vrow[ad[k]].dpos = q;
+        }
+        out += tot;
+        wave_sync();  // (the next chunk may read what this one wrote)
+    }
+    if (lane == 0) S.dtail[v] = out;
+}
+
+// wg_pack_prefix by one wave: the same decision and the same moves, lane l
+// taking the live entries of ranks l, l + 64, l + 128, l + 192 (the cap stays
+// PREFIX_CAP entries whatever the workgroup's size).  G, k: the longest prefix
+// of whole groups with at most PREFIX_CAP live entries, and their number (the
+// scan's count, wave_issue); sh.plist their positions.  Returns the head after it.
+__device__ uint32_t wave_pack_prefix(const SimDev& S, uint32_t v, WaveShared& sh, uint32_t head, uint32_t tail,
+                                     uint32_t base, uint32_t G, uint32_t k) {
+    static_assert(PREFIX_CAP == 4 * 64, "four entries per lane");
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint32_t n = S.n;
+    const uint32_t X = base + 64 * G;
+    if (k == 0 || X - head > tail - head || X - head < k + S.prefix_min) return head;
+    uint32_t* const lrow = S.dko + S.row(v);
+    uint64_t* const lvrow = S.dvs + S.row(v);
+    uint32_t* const larow = S.dad + S.row(v);
+    VEnt* const vrow = S.view + S.row(v);
+    const uint32_t hs = head % n;
+    auto slot = [&](uint32_t p) { const uint32_t sl = hs + (p - head); return sl >= n ? sl - n : sl; };
+    uint32_t w[4], a[4], pold[4];
+    uint64_t vs[4];
+    bool mv[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint32_t r = (uint32_t)j * 64u + lane;
+        mv[j] = false;
+        pold[j] = 0;
+        if (r < k) {
+            pold[j] = base + sh.plist[r];
+            mv[j] = pold[j] != X - k + r;
+        }
+    }
+    wave_sync();  // this issue's tombstones and stamp bumps have completed
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        w[j] = 0; a[j] = NONE; vs[j] = 0;
+        if (mv[j]) {
+            w[j] = lrow[slot(pold[j])];
+            a[j] = entry_addr(S, w[j], larow, slot(pold[j]));
+            if (!(w[j] & LOG_ALIVE)) vs[j] = lvrow[slot(pold[j])];
+        }
+    }
+    wave_sync();  // every source read before any write
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        if (mv[j]) {
+            const uint32_t P = X - k + (uint32_t)j * 64u + lane, i = slot(P);
+            lrow[i] = w[j];
+            if (!(w[j] & LOG_ALIVE)) { lvrow[i] = vs[j]; larow[i] = a[j]; }
+            vrow[a[j]].dpos = P;
+        }
+    }
+    if (lane == 0) { S.dhead[v] = X - k; stat_add(S, STAT_PREFIX_PACKS, 1); }
+    return X - k;
+}
+
+// PHASE 1: issueAsSender (no filter); 2: issueAsReceiver with the filter
+// (fsrc, finc).  dest is never NONE (its seen window is staged); sv: the
+// same-view decision (same_view_word), always precomputed here.
+template <bool ESC, int PHASE, int UNR = RP_WAVE_UNR>
+__device__ uint32_t wave_issue(const SimDev& S, uint32_t v, uint32_t fsrc, uint64_t finc, uint64_t* arena_off,
+                               WaveShared& sh, uint32_t dest, uint32_t* phys, uint32_t* phys_esc, uint64_t sv) {
+    const uint64_t dg_e = diag_clock();
+    const uint32_t n = S.n;
+    uint32_t* const lrow = S.dko + S.row(v);
+    const uint64_t* const lvrow = S.dvs + S.row(v);
+    const uint32_t* const larow = S.dad + S.row(v);
+    const SeenWin win = seen_window(S);
+    const uint32_t lane = (uint32_t)lane_id();
+    uint32_t s_lo = 0, s_hi = 0;
+    const uint32_t* const ssrc = seen_stage_src(S, dest, win, s_lo, s_hi);
+    // the node's scalars as uniform loads, then the arena reservation (the
+    // same per-slice cursors as wg_issue), the seen window (four 16-byte loads
+    // per lane, issued together) and the first groups' words all in flight
+    const uint32_t head = sload32(S.dhead + v), tail = sload32(S.dtail + v);
+    const uint32_t maxpb = sload32((const uint32_t*)S.max_pb + v), icount = sload32(S.icount + v);
+    const uint32_t dl0 = sload32(S.dlive + v);
+    const bool dang = sload32(S.dangerous) != 0;
+    const uint32_t a_shard = blockIdx.x % ARENA_SHARDS;
+    uint32_t a_res = 0;
+    if (lane == 0) a_res = atomicAdd((uint32_t*)&S.arena_cursor[a_shard * 16], dl0);
+    const uint32_t sw = S.seen_words;
+    uint4 st4[4];
+    if ((sw & 3u) == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint32_t i = (uint32_t)j * 64u + lane;
+            st4[j] = i < sw / 4 ? ((const uint4*)ssrc)[i] : uint4{0, 0, 0, 0};
+        }
+    }
+    const bool do_filter = PHASE == 2 && fsrc != NONE && finc != 0 && dang;
+    const uint32_t keep = (uint32_t)(sv >> 32), keep_pos = (uint32_t)sv;
+    const bool kall = keep == 0;
+    const uint32_t kpos = keep == 1 ? keep_pos : head - 1u;
+    // groups start at the head rounded down to 64 entries: a group's 64 slots
+    // are contiguous in the row
+    const uint32_t base = head & ~63u, base_slot = base % n;
+    const uint32_t hlo = head - base, span = tail - base;  // the window, relative to base
+    const uint32_t ngroups = (span + 63) / 64;
+    const uint32_t rowb = n * 4u;
+    const uint32_t lane4 = lane << 2;
+    const __amdgpu_buffer_rsrc_t rrow = __builtin_amdgcn_make_buffer_rsrc(lrow, (short)0, (int)rowb, 0x00020000);
+    // group offsets stay inside the row: a group of the window wraps at most
+    // once; one past the window (loaded with its batch, never used) reads slot 0
+    auto wrap = [&](uint32_t o) {
+        if (o >= rowb) o -= rowb;
+        return o >= rowb ? 0u : o;
+    };
+    uint32_t off0 = wrap(base_slot << 2);  // the byte offset of the next batch's first group
+    uint32_t nx[UNR];                      // ... and its words, loaded one batch ahead
+    auto load_batch = [&] {
+#pragma unroll
+        for (int u = 0; u < UNR; u++) nx[u] = __builtin_amdgcn_raw_buffer_load_b32(rrow, lane4, wrap(off0 + (uint32_t)u * 256u), 0);
+    };
+    load_batch();
+    if ((sw & 3u) == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint32_t i = (uint32_t)j * 64u + lane;
+            if (i < sw / 4) ((uint4*)sh.seen)[i] = st4[j];
+        }
+    } else {
+        for (uint32_t w = lane; w < sw; w += 64) sh.seen[w] = ssrc[w];
+    }
+    // the arena room (needed at the first store)
+    uint64_t aoff;
+    {
+        const uint64_t a_part = S.arena_cap / ARENA_SHARDS;
+        uint64_t o = (uint32_t)__builtin_amdgcn_readfirstlane(a_res);
+        if (o + dl0 > a_part) {
+            if (lane == 0) atomicOr(S.err, SIMERR_ARENA_FULL);
+            o = 0;
+        }
+        aoff = a_shard * a_part + o;
+    }
+    Change* const out = S.arena + aoff;
+    const uint64_t dg_pro = diag_clock() - dg_e;
+
+    uint32_t first_live = NONE, min_left = NONE, deleted = 0, emitted = 0, escapes = 0;
+    uint32_t min_safe = NONE;
+    uint64_t top1 = ~0ull, top2 = ~0ull;
+    uint32_t written = 0;         // entries stored so far
+    // prefix packing (wave_pack_prefix): whole groups of the first ISSUE_SEG,
+    // while their live entries number at most PREFIX_CAP
+    const uint32_t pfull = span >= 64u ? min(min(ISSUE_SEG, ngroups), span / 64u) : 0u;
+    uint32_t pG = 0, pk = 0;
+    bool pon = pfull != 0;  // (uniform) the prefix may still grow
+    uint32_t pend_h = 0, pend_t = 0;  // the pending ring (uniform; t - h < WAVE_PEND)
+    // store `cnt` <= 64 pending entries at out + written ..
+    auto flush = [&](uint32_t cnt) {
+        if (lane < cnt) {
+            const uint32_t e = (pend_h + lane) & (WAVE_PEND - 1u);
+            const uint32_t kv = sh.pw[e], sl = sh.ps[e];
+            const uint32_t pos = written + lane;
+            if (pos < dl0) store_msg(out + pos, log_change(S, kv, lvrow, larow, sl));
+            else atomicOr(S.err, SIMERR_ARENA_FULL);  // (cannot happen: written <= live keys)
+        }
+        pend_h += cnt;
+        written += cnt;
+    };
+    // group at row byte offset o: its written entries m (lane mask), words w
+    auto emit = [&](uint64_t m, uint32_t w, uint32_t o) {
+        if ((m >> lane) & 1ull) {
+            const uint32_t e = (pend_t + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))) &
+                               (WAVE_PEND - 1u);
+            sh.pw[e] = w;
+            sh.ps[e] = (uint16_t)((o >> 2) + lane);
+        }
+        pend_t += (uint32_t)__popcll(m);
+        if (pend_t - pend_h >= 64u) flush(64u);
+    };
+    const uint64_t dg_t = diag_clock();
+    if (!do_filter) {
+        // wg_issue's pass1_fast over consecutive groups
+        auto scan = [&](auto kall_t) {
+            constexpr bool KALL = decltype(kall_t)::value;
+            const uint32_t sspan = s_hi - s_lo;
+            const uint32_t smhi = win.smask & ~31u;  // the staged seen word's byte offset: (w & smhi) >> 3
+            uint32_t ud = 0, ue = 0, uesc = 0;       // expired, emitted, escapes (wave sums)
+            uint32_t ml1 = NONE, ms1 = NONE;         // the smallest count c1 = c2 - 1 (left, safe)
+            const uint32_t tomb = TOMB_WORD, none = NONE, one = 1u, zero = 0u;
+            auto sel = [](uint64_t mask, uint32_t t, uint32_t f) {
+                const uint64_t ms = rfl64(mask);
+                uint32_t r;
+                asm volatile("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(f), "v"(t), "s"(ms));
+                return r;
+            };
+            auto bit = [&](uint64_t mask) { return sel(mask, one, zero) != 0u; };
+            auto sel_s = [](uint64_t mask, uint32_t t, uint32_t f) {
+                uint32_t r;
+                asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(f), "v"(t), "s"(mask));
+                return r;
+            };
+            // the groups the window does not cut: g_lo <= g < g_lo + g_n
+            const uint32_t g_lo = hlo ? 1u : 0u, g_hi = span >> 6;
+            const uint32_t g_n = g_hi > g_lo ? g_hi - g_lo : 0u;
+            for (uint32_t q0 = 0; q0 < ngroups; q0 += UNR) {
+                uint32_t ko[UNR];
+#pragma unroll
+                for (int u = 0; u < UNR; u++) ko[u] = nx[u];
+                const uint32_t offc = off0;
+                off0 = wrap(off0 + UNR * 256u);
+                if (q0 + UNR < ngroups) load_batch();  // the next batch, ahead of this one's work
+#pragma unroll
+                for (int u = 0; u < UNR; u++) {
+                    const uint32_t g = q0 + u, gp = g * 64u;
+                    if (g >= ngroups) break;  // uniform
+                    const uint32_t o = wrap(offc + (uint32_t)u * 256u);
+                    uint32_t w = ko[u];
+                    if (__builtin_expect(g - g_lo >= g_n, 0)) {
+                        // the window's lanes of a group it cuts (its first or its last)
+                        const uint32_t lo = gp < hlo ? hlo - gp : 0u, hi = min(span - gp, 64u);
+                        w = sel((hi >= 64u ? ~0ull : ((1ull << hi) - 1ull)) & ~((1ull << lo) - 1ull), w, tomb);
+                    }
+                    const uint32_t c1 = (icount - (w >> 24)) & STAMP_MASK;  // an undefined count counts as 0
+                    const uint64_t mnt = __ballot((w & LOG_ORIGIN_MASK) != ORIGIN_ID_MASK);
+                    const uint64_t mge = __ballot(c1 >= maxpb);       // c1 + 1 > maxpb: lib/dissemination.js:162-165
+                    const uint64_t mex = mnt & mge, lm = mnt & ~mge;  // expire now / stay live
+                    if (mex && bit(mex))  // (the cell keeps its stale log position: wg_apply checks it)
+                        __builtin_amdgcn_raw_buffer_store_b32(TOMB_WORD, rrow, lane4, o, 0);
+                    const uint64_t mla = __ballot((w & LOG_ALIVE) != 0);
+                    const uint32_t sw1 = *(const uint32_t*)((const char*)sh.seen + ((w & smhi) >> 3));
+                    uint64_t m = lm & ~(mla & __ballot(((w - s_lo) & ORIGIN_ID_MASK) < sspan) &
+                                        __ballot(__builtin_amdgcn_ubfe(sw1, w, 1u) != 0));
+                    if constexpr (!KALL) {  // only the entry at kpos may be written
+                        const uint32_t kl = kpos - (base + gp);
+                        m &= kl < 64u ? (1ull << kl) : 0ull;
+                    }
+                    ud += (uint32_t)__popcll(mex);
+                    ue += (uint32_t)__popcll(lm);
+                    if (ESC) uesc += (uint32_t)__popcll(m & ~mla);
+                    ml1 = min(ml1, sel_s(lm, c1, none));
+                    if (PHASE == 1) {
+                        const uint64_t mu = lm & ~(mla | __ballot((w & ORIGIN_ID_MASK) < S.lorigin_base));
+                        ms1 = min(ms1, sel_s(lm & ~mu, c1, none));
+                        if (mu && bit(mu))  // (unsafe live entries: local suspect/faulty origins)
+                            top2_insert(top1, top2, ((uint64_t)(c1 + 1u) << 32) | S.origins[w & ORIGIN_ID_MASK].source);
+                    }
+                    if (pon) {  // (uniform; ue: the live entries up to and with this group)
+                        pon = g < pfull && ue <= PREFIX_CAP;
+                        if (pon) {
+                            if (lm && bit(lm))
+                                sh.plist[ue - (uint32_t)__popcll(lm) +
+                                         __builtin_amdgcn_mbcnt_hi((uint32_t)(lm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lm, 0u))] =
+                                    (uint16_t)(gp + lane);
+                            pG = g + 1u;
+                            pk = ue;
+                        }
+                    }
+                    if (__builtin_expect(first_live == NONE, 0) && lm)
+                        first_live = base + gp + (uint32_t)__builtin_ctzll(lm);
+                    if (m) emit(m, w, o);  // (uniform)
+                }
+            }
+            min_left = ml1 == NONE ? NONE : ml1 + 1u;
+            if (PHASE == 1) min_safe = ms1 == NONE ? NONE : ms1 + 1u;
+            deleted = ud; emitted = ue; escapes = uesc;
+        };
+        if (kall) scan(std::true_type{});
+        else scan(std::false_type{});
+    } else {
+        // issueAsReceiver with a filter that can match (suspect/faulty origins
+        // exist: rare without faults, the wire bridge): wg_issue's
+        // pass1(true_type) per lane, a group at a time
+        uint32_t nlive = 0;
+        for (uint32_t g = 0; g < ngroups; g++) {
+            const uint32_t p = base + g * 64u + lane;
+            const uint32_t o = wrap(off0);
+            off0 = wrap(off0 + 256u);
+            const uint32_t sl = (o >> 2) + lane;
+            const bool inw = p - head < tail - head;
+            const uint32_t w = inw ? lrow[sl] : TOMB_WORD;
+            const uint32_t org = log_origin(w);
+            bool wr = false, alive = false, f_ex = false, f_em = false;
+            if (!is_tomb(w)) {
+                uint32_t c2 = entry_count(w, icount);  // an undefined count counts as 0 (:149-151)
+                const Origin og = S.origins[origin_slot(S, org)];
+                const bool filtered = og.source != NONE && og.source_inc != 0 && og.source == fsrc && og.source_inc == finc;
+                alive = true;
+                if (filtered) {  // count stays: bump the stamp along with the issue counter
+                    lrow[sl] = (w & LOG_ORIGIN_MASK) | (((((w >> 24) + 1) & STAMP_MASK) | STAMP_DEFINED) << 24);
+                } else {
+                    c2 += 1;
+                    if (c2 > maxpb) {  // lib/dissemination.js:162-165
+                        f_ex = true;
+                        alive = false;
+                        lrow[sl] = TOMB_WORD;
+                    } else {
+                        f_em = true;
+                        const uint32_t oi = org & ORIGIN_ID_MASK;
+                        const bool seen = (org & ORIGIN_ALIVE) && ((oi - s_lo) & ORIGIN_ID_MASK) < s_hi - s_lo &&
+                                          ((sh.seen[(oi & win.smask) >> 5] >> (oi & 31)) & 1u);
+                        wr = !seen && (kall || p == kpos);
+                    }
+                }
+                if (alive) min_left = min(min_left, c2);
+            }
+            deleted += (uint32_t)__popcll(__ballot(f_ex));
+            emitted += (uint32_t)__popcll(__ballot(f_em));
+            const uint64_t m = __ballot(wr), lm = __ballot(alive);
+            if (ESC) escapes += (uint32_t)__popcll(m & ~__ballot((w & LOG_ALIVE) != 0));
+            if (pon) {  // (emitted + filtered: the live entries up to and with this group)
+                nlive += (uint32_t)__popcll(lm);
+                pon = g < pfull && nlive <= PREFIX_CAP;
+                if (pon) {
+                    if (alive)
+                        sh.plist[nlive - (uint32_t)__popcll(lm) + (uint32_t)__popcll(lm & ((1ull << lane) - 1ull))] =
+                            (uint16_t)(g * 64u + lane);
+                    pG = g + 1u;
+                    pk = nlive;
+                }
+            }
+            if (first_live == NONE && lm) first_live = base + g * 64u + (uint32_t)__builtin_ctzll(lm);
+            if (m) emit(m, w, o);
+        }
+    }
+    if (pend_t != pend_h) flush(pend_t - pend_h);
+    const uint64_t dg_ep = diag_clock();
+    if (PHASE == RP_DIAG_PHASE) { DIAG_ADD(S, 0, dg_ep - dg_t); DIAG_ADD(S, 2, dg_pro); }
+    (void)dg_t; (void)dg_pro; (void)dg_ep;
+    // reductions within the wave: the counts and first_live are uniform
+    // already; the minima per lane; the top-2 keys only when a lane holds one
+    {
+        const bool tops = PHASE == 1 && __ballot(top1 != ~0ull) != 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            min_left = min(min_left, (uint32_t)__shfl_xor(min_left, o));
+            if (PHASE == 1) min_safe = min(min_safe, (uint32_t)__shfl_xor(min_safe, o));
+            if (tops) {
+                const uint64_t b1 = __shfl_xor(top1, o), b2 = __shfl_xor(top2, o);
+                top2_insert(top1, top2, b1);
+                top2_insert(top1, top2, b2);
+            }
+        }
+    }
+    const uint32_t nh = first_live == NONE ? tail : first_live, nl = dl0 - deleted;
+    const bool compact = (tail - nh) > S.compact_mul * nl + S.compact_add;  // mostly tombstones: compact
+    if (lane == 0) {
+        S.icount[v] = icount + 1;
+        if (nh != head) S.dhead[v] = nh;
+        if (deleted) S.dlive[v] = nl;
+        if (PHASE == 1) { S.min_cnt[v] = min_left; S.min_safe[v] = min_safe; S.min_l1[v] = top1; S.min_l2[v] = top2; }
+        stat_add(S, PHASE == 1 ? STAT_SCANNED_P1 : STAT_SCANNED_P2, (unsigned long long)(tail - head));
+        stat_add(S, PHASE == 1 ? STAT_EMITTED_P1 : STAT_EMITTED_P2, (unsigned long long)emitted);
+        stat_add(S, PHASE == 1 ? STAT_WRITTEN_P1 : STAT_WRITTEN_P2, (unsigned long long)written);
+        stat_add(S, STAT_WAVE_ISSUES, 1);
+        if (compact) stat_add(S, STAT_COMPACT_ISSUE, 1);
+    }
+    *arena_off = aoff;
+    const uint32_t ph = wave_pack_prefix(S, v, sh, nh, tail, base, pG, pk);
+    if (PHASE == RP_DIAG_PHASE) DIAG_ADD(S, 4, diag_clock() - dg_ep);
+    if (compact) {
+        wave_sync();  // the issue's tombstones and the packing's moves have completed
+        wave_compact(S, v, ph, tail);
+    }
+    *phys = written;
+    *phys_esc = escapes;
+    return emitted;
+}
+
 // ---------------------------------------------------------------- init
 __global__ void k_init_rows(SimDev S) {
     const uint64_t total = (uint64_t)S.nl * S.n;
@@ -2136,6 +2583,36 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(RP_P
     uint32_t m = wg_issue<ESC, RP_ISSUE_UNR_P1, SET, SET && RP_SETTLED_PF, true>(S, v, false, NONE, 0, &off, 1, sh,
                                                      tl ? (uint32_t)T : ((uint32_t)T | DEST_REMOTE), &pm, &pe,
                                                      FP_NONE, sv);  // issueAsSender (ping-sender.js:70)
+    if (threadIdx.x == 0) {
+        S.msg_off[v] = off;
+        S.msg_len[v] = m;
+        S.msg_plen[v] = pm;
+        S.msg_nesc[v] = pe;
+        S.snd_inc[v] = v_inc(svs);  // getIncarnationNumber()
+        S.snd_fp[v] = sfp;
+        stat_add(S, STAT_PINGS, 1ull);
+        stat_add(S, STAT_MESSAGES, 1ull);
+    }
+}
+// k_phase1 with one wave per node (wave_issue): runs without faults on
+// 64-aligned rows.  The same stores, and the same target counting: every
+// node with T >= 0 is counted exactly once (k_group_fill2 trusts it, see
+// Shard::stage_checksums).
+template <bool ESC>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RP_WAVE_WAVES, RP_WAVE_WAVES)))
+k_phase1_wave(SimDev S) {
+    __shared__ WaveShared sh;
+    const uint32_t v = S.lo + blockIdx.x;
+    const int32_t T = S.target[v];
+    const uint64_t svs = S.view[S.row(v) + v].vs, sfp = S.fp[v];
+    const uint64_t sv = sload64(S.sv_word + v);
+    if (T < 0) return;
+    if (S.nranks == 1 && threadIdx.x == 0) atomicAdd(&S.g_cnt[T], 1u);
+    uint64_t off;
+    uint32_t pm, pe;
+    const bool tl = S.local((uint32_t)T);
+    const uint32_t m = wave_issue<ESC, 1>(S, v, NONE, 0, &off, sh, tl ? (uint32_t)T : ((uint32_t)T | DEST_REMOTE), &pm,
+                                          &pe, sv);  // issueAsSender (ping-sender.js:70)
     if (threadIdx.x == 0) {
         S.msg_off[v] = off;
         S.msg_len[v] = m;
@@ -3413,6 +3890,73 @@ k_p2_respond(SimDev S, uint32_t k, const P2Rec* rec, const uint32_t* len) {
         return;
     }
     respond_as_receiver<ESC, SET, SET && RP_SETTLED_PF, true>(S, b, A, req_inc, req_fp, 0u, need, A, 0, sh, sv, true);
+}
+// k_p2_respond with one wave per receiver (wave_issue): respond_as_receiver's
+// record, pending-fullSync bookkeeping and snapshot copy by 64 lanes.
+template <bool ESC>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RP_WAVE_WAVES, RP_WAVE_WAVES)))
+k_p2_respond_wave(SimDev S, const P2Rec* rec, const uint32_t* len) {
+    __shared__ WaveShared sh;
+    uint32_t w[8];
+    sload_words(rec + blockIdx.x, w);
+    const uint32_t b = w[0], Ad = w[1];
+    const uint64_t sv = ((uint64_t)w[3] << 32) | w[2];
+    const uint64_t req_inc = ((uint64_t)w[5] << 32) | w[4], req_fp = ((uint64_t)w[7] << 32) | w[6];
+    if (blockIdx.x >= *len) return;
+    const uint32_t A = Ad & ~(P2_DEAD | P2_NEED);
+    const bool need = (Ad & P2_NEED) != 0;
+    if (Ad & P2_DEAD) {  // down or cut off: transport error one wave later
+        if (threadIdx.x == 0) {
+            Resp rr{};
+            rr.kind = RESP_ERR; rr.from = b; rr.snap = NONE;
+            S.resp[A] = rr;
+            stat_add(S, STAT_MESSAGES, 1ull);
+        }
+        return;
+    }
+    const uint32_t n = S.n;
+    uint64_t off;
+    uint32_t pm, pe;
+    const uint32_t m = wave_issue<ESC, 2>(S, b, A, req_inc, &off, sh, S.local(A) ? A : (A | DEST_REMOTE), &pm, &pe, sv);
+    uint32_t snap = NONE;  // lane 0: the snapshot slot of a pending fullSync decision
+    if (threadIdx.x == 0) {
+        Resp r;
+        r.kind = RESP_LIST; r.from = b; r.off = off; r.len = m; r.snap = NONE; r.ping_status = 0;
+        r.plen = pm;
+        r.nesc = pe;
+        r.eoff = 0;
+        if (m == 0) {
+            if (S.fp[b] == req_fp) {
+                r.kind = RESP_EMPTY;  // identical views: identical checksums
+            } else if (!need) {
+                atomicOr(S.err, SIMERR_PREDICATE);
+                r.kind = RESP_EMPTY;
+            } else {
+                const uint32_t k = atomicAdd(S.snap_count, 1u);
+                if (k >= S.snap_cap) { atomicOr(S.err, SIMERR_SNAP_FULL); r.kind = RESP_EMPTY; }
+                else {
+                    r.kind = RESP_FS_PENDING; r.snap = k;
+                    S.pend_slot[k] = A | PEND_SND;  // (k_pending compares with snd_csum[A])
+                    S.pend_csum[k] = 0u;
+                    snap = k;
+                }
+            }
+        }
+        S.resp[A] = r;
+        stat_add(S, STAT_MESSAGES, 1ull);
+    }
+    snap = __builtin_amdgcn_readfirstlane(snap);
+    if (snap != NONE) {  // snapshot the view for a possible fullSync() (read in later kernels)
+        uint64_t* dst = S.snaps + (size_t)snap * n;
+        const VEnt* srow = S.view + S.row(b);
+        for (uint32_t a = threadIdx.x; a < n; a += 64) dst[a] = srow[a].vs;
+        // ... with the member order it lists them in (later batches may splice)
+        const uint32_t M = S.mcount[b];
+        uint32_t* dord = S.snap_ord + (size_t)snap * n;
+        const uint32_t* sord = S.order + S.row(b);
+        for (uint32_t i = threadIdx.x; i < M; i += 64) dord[i] = sord[i];
+        if (threadIdx.x == 0) S.snap_m[snap] = M;
+    }
 }
 
 template <bool ESC, bool JOIN, bool SET>
@@ -5454,6 +5998,12 @@ struct Shard {
     uint32_t npts = 0, ncoll = 0, seen_words = 0;
     bool join_mode = false;  // views may lack members: the JOIN merge kernels
     bool fault_mode = false;  // fail-stops, storms or partitions scheduled: the settled-filter issue kernels
+    bool issue_wave = RP_ISSUE_WAVE != 0;  // rp_sim_config.issue_wave: the one-wave issue kernels where eligible
+    // k_phase1 / k_p2_respond as one wave per node (wave_issue): runs without
+    // faults or joins, rows of whole 64-entry groups, a seen window that fits its LDS
+    bool wave_issue_ok() const {
+        return issue_wave && !fault_mode && !join_mode && n % 64 == 0 && seen_words <= rp::SEEN_STAGE_WORDS;
+    }
     // join replies of a round (rp_sim_join): per pair its seed's view, member
     // order / count and checksum (filled on the seed's shard, then shared)
     DevBuf<uint64_t> jvs;
@@ -5969,6 +6519,7 @@ void Shard::setup() {
     else { d.compact_mul = RP_COMPACT_MUL; d.compact_add = RP_COMPACT_ADD; }
     d.prefix_min = cfg.prefix_min ? cfg.prefix_min : RP_PREFIX_MIN;
     d.ck_lane_min = cfg.ck_lane_min ? cfg.ck_lane_min : RP_CK_LANE_MIN;
+    if (cfg.issue_wave) issue_wave = cfg.issue_wave == 2;
     {
         // seen groups: the largest power of two up to 2^cap dividing the shard
         // size.  In process the mask all-gather is a device copy and per-node
@@ -6241,7 +6792,10 @@ void Shard::stage_issue() {
         // grid strides over them and leaves the CUs to the other shards' work)
         hipLaunchKernelGGL(k_shuffle, dim3(std::min<uint32_t>(nl, 32)), dim3(BLOCK), (size_t)n * 2, st, d,
                            need_shuffle.p, 1, (const uint32_t*)shuf_list.p, (const uint32_t*)shuf_count.p);
-        if (fault_mode) {
+        if (wave_issue_ok()) {
+            if (G > 1) hipLaunchKernelGGL(k_phase1_wave<true>, dim3(nl), dim3(64), 0, st, d);
+            else hipLaunchKernelGGL(k_phase1_wave<false>, dim3(nl), dim3(64), 0, st, d);
+        } else if (fault_mode) {
             if (G > 1) hipLaunchKernelGGL((k_phase1<true, true>), dim3(nl), dim3(BLOCK), 0, st, d);
             else hipLaunchKernelGGL((k_phase1<false, true>), dim3(nl), dim3(BLOCK), 0, st, d);
         } else {
@@ -6254,6 +6808,11 @@ void Shard::stage_issue() {
 void Shard::stage_checksums() {
     using namespace rp;
     // (the group counts, ck_count and the dedupe table were reset by stage_start's launch)
+    // One shard: the counts are already made -- k_phase1 / k_phase1_wave count
+    // every node with target[v] >= 0 exactly once -- and k_group_fill2 places
+    // each slot at list[base of its target + fill] with bases scanned from
+    // those counts, never re-counting target[]: an issue kernel that skipped
+    // or repeated a count would make the lists overlap or leave gaps, silently.
     timed(5, [&] { group(target.p, n, true, G == 1); });
     timed(4, [&] {
         // (one shard: its own count is the cluster's; a shard of several
@@ -6279,7 +6838,10 @@ void Shard::stage_ping_merge(uint64_t now) {
             else hipLaunchKernelGGL(k_p2_apply<false>, grid, dim3(BLOCK), 0, st, d, now, k, lk, p2_len.p + k, mk);
             hipLaunchKernelGGL(k_p2_pre, dim3(grid_for(grid.x, 256)), dim3(256), 0, st, d, lk, p2_len.p + k, p2_rec.p);
             const P2Rec* rk = p2_rec.p;
-            if (fault_mode) {
+            if (wave_issue_ok()) {
+                if (G > 1) hipLaunchKernelGGL(k_p2_respond_wave<true>, grid, dim3(64), 0, st, d, rk, p2_len.p + k);
+                else hipLaunchKernelGGL(k_p2_respond_wave<false>, grid, dim3(64), 0, st, d, rk, p2_len.p + k);
+            } else if (fault_mode) {
                 if (G > 1) hipLaunchKernelGGL((k_p2_respond<true, true>), grid, dim3(BLOCK), 0, st, d, k, rk, p2_len.p + k);
                 else hipLaunchKernelGGL((k_p2_respond<false, true>), grid, dim3(BLOCK), 0, st, d, k, rk, p2_len.p + k);
             } else {
