@@ -384,8 +384,8 @@ int rp_sim_address(rp_sim *sim, uint32_t node, char *buf, size_t cap);
  * destination's ring is the destination itself, else 0 (such a request counts
  * in `misrouted`; for the other outcomes it is 0).  dests, outcomes and
  * owner_agrees may each be NULL; stats->requests is the sum of the five
- * outcome counts.  Retries are not modelled: a caller models send.js's
- * schedule (:267-294) by routing the failed subset again after more rounds.
+ * outcome counts.  A route is one instant: requests that retry across rounds
+ * (send.js:267-294) are rp_traffic_*'s, below.
  *
  * rp_sim_route_uniform: the same for `count` requests generated on the
  * device, only the statistics returned.  Request i (0-based) is
@@ -403,6 +403,117 @@ int rp_sim_ring_checksums(rp_sim *sim, uint32_t *out, size_t cap);
 int rp_sim_route(rp_sim *sim, const uint32_t *entries, const uint32_t *key_hashes, size_t n, int32_t *dests,
                  uint8_t *outcomes, uint8_t *owner_agrees, rp_route_stats *stats);
 int rp_sim_route_uniform(rp_sim *sim, uint64_t seed, uint64_t count, rp_route_stats *stats);
+
+/* ---- Request traffic with proxy retries across rounds ------------------------
+ * Replaces the RequestProxySend state machine (lib/request-proxy/send.js) for
+ * batches of single-key requests that live across rounds: a tracker keeps a
+ * request table on its simulation's device and advances it between rounds
+ * (DESIGN.md §11).  Its clock is the number of rounds run so far, as for
+ * rp_sim_route: a partition window and a fail-stop scheduled for round k are
+ * tested the same way.  A request is (entry e, key hash h) and gets a 64-bit
+ * id in submission order.  "lookup" is HashRing.lookup(h) in e's view at the
+ * current clock (an empty ring gives e).  Line numbers are send.js's unless
+ * marked.
+ *   1 first attempt, at submission (index.js:607-634): e fail-stopped: final
+ *     ENTRY_DEAD.  d0 = lookup; d0 == e: final LOCAL.  Otherwise proxied++ and
+ *     send(e -> d0).
+ *   2 send(e -> d): d fail-stopped or the partition between them:
+ *     send_unreachable++, an error.  Else, when the two nodes' ring checksums
+ *     differ: checksums_differ++, an error with enforce_consistency
+ *     (lib/request-proxy/index.js:172-187), a success without.  A success is
+ *     final DELIVERED with dest d; retry_succeeded++ after at least one retry
+ *     (:158-167); misrouted++ when the lookup of h in d's own view is not d
+ *     (rp_sim_route's owner_agrees rule).
+ *   3 on an error (:286-293): retries >= max_retries: final FAILED (dest: the
+ *     last destination tried), retry_failed++ unless max_retries is 0 (:261,
+ *     :296-304 raise the plain error).  Otherwise retry_scheduled++ and due =
+ *     clock + schedule[min(retries, nschedule - 1)] (an index past the end
+ *     takes the last entry, as numOrDefault does, :216-217).
+ *   4 retry, at the first poll whose clock is >= due (:105-127): e
+ *     fail-stopped: final ENTRY_DEAD, nothing else counted.  Otherwise
+ *     retries++, retry_attempted++, nd = lookup, compared with the ORIGINAL d0
+ *     (channelOpts.host is never updated, :121; a reroute passes other
+ *     options to send only, :200-205).  nd == d0: proxied++, send(e -> d0).
+ *     Otherwise retry_rerouted++; nd == e: final REROUTED_LOCAL (handleRequest
+ *     with e's own checksum; not through handleSuccess, :188-196); else
+ *     proxied++, send(e -> nd).
+ *   5 a delay of 0 is taken at the same clock in the same call: a call loops a
+ *     request until it is final or due later (at most max_retries + 1
+ *     attempts).  Requests never change membership state, so their order
+ *     changes no result.
+ * Multi-key requests (handleOrProxyAll, abortOnKeyDivergence :90-113) are out
+ * of scope.  On one rank of a multi-process or loop cluster rp_traffic_create
+ * returns RP_ERR_UNSUPPORTED.  Destroy a tracker before its simulation. */
+typedef struct rp_traffic rp_traffic;
+typedef struct {
+    int32_t max_retries;         /* 0..8; < 0 = the default, 3 */
+    uint32_t nschedule;          /* delays in schedule[], <= 8; 0 = the default {0, 5, 18}: RETRY_SCHEDULE
+                                    [0, 1, 3.5] s (:49) in 200 ms periods, rounded up */
+    uint32_t schedule[8];        /* rounds */
+    int32_t enforce_consistency; /* < 0 = the default, 1 (lib/request-proxy/index.js:49) */
+    uint32_t track;              /* keep a final record per request (rp_traffic_results) */
+    uint32_t timing;             /* HIP events around every poll and submit (rp_traffic_times) */
+    uint32_t reserved;
+    uint64_t capacity;           /* most records the pending table may hold (<= 2^30); 0 = 2^20 */
+} rp_traffic_config;
+typedef struct {
+    uint64_t submitted, local, delivered, rerouted_local, failed, entry_dead, proxied, send_unreachable,
+        checksums_differ, retry_scheduled, retry_attempted, retry_rerouted, retry_succeeded, retry_failed,
+        misrouted, reserved;
+} rp_traffic_stats;
+#define RP_REQUEST_LOCAL 0
+#define RP_REQUEST_DELIVERED 1
+#define RP_REQUEST_REROUTED_LOCAL 2
+#define RP_REQUEST_FAILED 3
+#define RP_REQUEST_ENTRY_DEAD 4
+#define RP_REQUEST_PENDING 255
+typedef struct {
+    int32_t dest;          /* LOCAL, REROUTED_LOCAL: the entry; DELIVERED: where; FAILED: the last destination
+                              tried; ENTRY_DEAD: -1; pending: the first destination */
+    uint8_t outcome;       /* RP_REQUEST_* */
+    uint8_t retries;
+    uint16_t reserved;
+    uint32_t submit_clock;
+    uint32_t done_clock;   /* pending: 0 */
+} rp_request_result;
+typedef struct {
+    uint64_t id;
+    uint32_t entry, key_hash;
+    int32_t first_dest;    /* d0 */
+    uint32_t due;          /* the clock its next retry is due at */
+    uint32_t submit_clock;
+    uint32_t retries;
+} rp_request_pending;
+int rp_traffic_create(rp_sim *sim, const rp_traffic_config *cfg, rp_traffic **out); /* cfg NULL: the defaults */
+int rp_traffic_destroy(rp_traffic *traffic);
+/* n requests make their first attempts now; *first_id (may be NULL) = the id of request 0 */
+int rp_traffic_submit(rp_traffic *traffic, const uint32_t *entries, const uint32_t *key_hashes, size_t n,
+                      uint64_t *first_id);
+/* the same for requests first .. first + count - 1 of rp_sim_route_uniform's generator with `seed`, drawn on the
+ * device; nothing is allocated per request */
+int rp_traffic_submit_uniform(rp_traffic *traffic, uint64_t seed, uint64_t first, uint64_t count);
+/* every pending request that is due retries */
+int rp_traffic_poll(rp_traffic *traffic);
+/* k times: one round (rp_sim_round), a poll, a submit_uniform of per_round requests whose generator index continues
+ * from the requests earlier rp_traffic_run calls on this tracker drew (0 at first); equal to those calls made one
+ * by one, with no readback per round beyond rp_sim_round's error check */
+int rp_traffic_run(rp_traffic *traffic, int k_rounds, int churn_active, uint64_t per_round, uint64_t seed);
+/* cumulative statistics and by_retries[outcome * 9 + r]: final requests per outcome (5) and retry count r = 0..8
+ * (either may be NULL) */
+int rp_traffic_read_stats(rp_traffic *traffic, rp_traffic_stats *cumulative, uint64_t *by_retries);
+/* rows[i] = what happened in calls made at clock first_clock + i (zero where none was) */
+int rp_traffic_history(rp_traffic *traffic, uint32_t first_clock, uint32_t count, rp_traffic_stats *rows);
+/* the pending table in submission order; *count = its length; out may be NULL, else cap >= that length */
+int rp_traffic_pending(rp_traffic *traffic, rp_request_pending *out, size_t cap, uint64_t *count);
+/* the records of requests first_id .. first_id + n - 1 (track only) */
+int rp_traffic_results(rp_traffic *traffic, uint64_t first_id, size_t n, rp_request_result *out);
+/* timing only: device ms and calls of {polls, submits} since creation; the largest pending count so far (measurement,
+ * no reference counterpart; any may be NULL) */
+int rp_traffic_times(rp_traffic *traffic, double *ms2, uint64_t *calls2, uint64_t *peak_pending);
+/* Capacity: the pending table grows on demand up to `capacity` and never drops a request: submit presizes it for
+ * pending + n, run for pending + per_round x min(k_rounds, the retry delays' sum + 1) -- a request stays pending for
+ * at most the sum of the delays of its max_retries retries -- and a call that would need more fails with
+ * RP_ERR_CAPACITY before any state changes. */
 
 /* per-kernel device time (HIP events on the simulation stream), ms, summed
  * since enable; names: churn, issue(phase1), merge_ping(phase2),

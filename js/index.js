@@ -601,6 +601,53 @@ SimCluster.ROUTE_OUTCOMES = ['local', 'delivered', 'checksumsDiffer', 'unreachab
 SimCluster.prototype.route = function route(entries, keyHashes) {
     return addon.simRoute(this._sim, entries, keyHashes);
 };
+// Request traffic with the request proxy's retries across rounds
+// (rp_traffic_*; lib/request-proxy/send.js): opts {maxRetries: 3, schedule:
+// [0, 5, 18] rounds, enforceConsistency: true, track: false, capacity: 2^20}.
+// The tracker's clock is the cluster's round count.  Statistics carry the
+// reference's event names where it has one (requestProxied, checksumsDiffer,
+// retryScheduled, retryAttempted, retryRerouted, retrySucceeded, retryFailed).
+function Traffic(cluster, opts) {
+    opts = opts || {};
+    var o = {};
+    if (opts.maxRetries !== undefined) o.maxRetries = opts.maxRetries;
+    if (opts.schedule !== undefined) o.schedule = opts.schedule;
+    if (opts.enforceConsistency !== undefined) o.enforceConsistency = opts.enforceConsistency ? 1 : 0;
+    if (opts.track) o.track = 1;
+    if (opts.capacity !== undefined) o.capacity = opts.capacity;
+    this._cluster = cluster;
+    this._t = addon.trafficCreate(cluster._sim, o);
+}
+Traffic.OUTCOMES = ['local', 'delivered', 'reroutedLocal', 'failed', 'entryDead'];
+Traffic.PENDING = 255;
+// first attempts now of request i = (entries[i], keyHashes[i]) (Uint32Arrays); the id of request 0
+Traffic.prototype.submit = function submit(entries, keyHashes) {
+    return addon.trafficSubmit(this._t, entries, keyHashes);
+};
+// requests first .. first + count - 1 of the device generator (rp_sim_route_uniform's)
+Traffic.prototype.submitUniform = function submitUniform(seed, first, count) {
+    addon.trafficSubmitUniform(this._t, seed, first, count);
+};
+// every pending request that is due retries
+Traffic.prototype.poll = function poll() { addon.trafficPoll(this._t); };
+// k times: a round, a poll, a submitUniform of perRound requests
+Traffic.prototype.run = function run(k, perRound, seed, churn) {
+    addon.trafficRun(this._t, k, churn !== false, perRound, seed);
+};
+// {stats, byRetries: {outcome: [finals with 0..8 retries]}}
+Traffic.prototype.stats = function stats() {
+    var r = addon.trafficStats(this._t), by = {};
+    Traffic.OUTCOMES.forEach(function (k, i) { by[k] = Array.from(r.byRetries.subarray(9 * i, 9 * i + 9)); });
+    return { stats: r.stats, byRetries: by };
+};
+Traffic.prototype.history = function history(firstClock, count) {
+    return addon.trafficHistory(this._t, firstClock, count);
+};
+Traffic.prototype.pending = function pending() { return addon.trafficPending(this._t); };
+Traffic.prototype.results = function results(firstId, n) { return addon.trafficResults(this._t, firstId, n); };
+Traffic.prototype.close = function close() { addon.trafficClose(this._t); };
+SimCluster.prototype.traffic = function traffic(opts) { return new Traffic(this, opts); };
+SimCluster.Traffic = Traffic;
 SimCluster.prototype.addresses = function addresses() {
     if (!this._addr) {
         this._addr = [];

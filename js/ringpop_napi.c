@@ -581,6 +581,303 @@ static napi_value js_sim_route(napi_env env, napi_callback_info info) {
     return o;
 }
 
+/* ---- request traffic with proxy retries (rp_traffic_*): a tracker handle keeps
+ * its simulation's handle alive until it is closed or collected */
+typedef struct {
+    rp_traffic *t;
+    napi_ref sim_ref;
+} traffic_handle;
+
+static void traffic_release(napi_env env, traffic_handle *h) {
+    if (h->t) rp_traffic_destroy(h->t);
+    h->t = NULL;
+    if (h->sim_ref) napi_delete_reference(env, h->sim_ref);
+    h->sim_ref = NULL;
+}
+
+static void traffic_finalize(napi_env env, void *data, void *hint) {
+    (void)hint;
+    traffic_release(env, (traffic_handle *)data);
+    free(data);
+}
+
+static rp_traffic *get_traffic(napi_env env, napi_value v) {
+    traffic_handle *h = (traffic_handle *)get_external(env, v);
+    if (!h || !h->t) {
+        napi_throw_error(env, NULL, "traffic tracker is closed");
+        return NULL;
+    }
+    return h->t;
+}
+
+/* trafficCreate(sim, {maxRetries, schedule: [rounds], enforceConsistency, track, capacity}) */
+static napi_value js_traffic_create(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2], ext;
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    rp_traffic_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.max_retries = -1;
+    cfg.enforce_consistency = -1;
+    if (argc > 1) {
+        napi_valuetype vt = napi_undefined;
+        napi_typeof(env, argv[1], &vt);
+        if (vt == napi_object) {
+            cfg.max_retries = (int32_t)get_num_prop(env, argv[1], "maxRetries", -1);
+            cfg.enforce_consistency = (int32_t)get_num_prop(env, argv[1], "enforceConsistency", -1);
+            cfg.track = get_num_prop(env, argv[1], "track", 0) != 0;
+            cfg.capacity = (uint64_t)get_num_prop(env, argv[1], "capacity", 0);
+            bool has = false;
+            napi_has_named_property(env, argv[1], "schedule", &has);
+            if (has) {
+                napi_value arr, v;
+                uint32_t len = 0;
+                napi_get_named_property(env, argv[1], "schedule", &arr);
+                if (napi_get_array_length(env, arr, &len) != napi_ok || len < 1 || len > 8) {
+                    napi_throw_range_error(env, NULL, "schedule must be an array of 1 to 8 delays in rounds");
+                    return NULL;
+                }
+                cfg.nschedule = len;
+                for (uint32_t i = 0; i < len; i++) {
+                    double d = 0;
+                    napi_get_element(env, arr, i, &v);
+                    napi_get_value_double(env, v, &d);
+                    cfg.schedule[i] = d < 0 ? 0 : (uint32_t)d;
+                }
+            }
+        }
+    }
+    traffic_handle *h = (traffic_handle *)calloc(1, sizeof *h);
+    if (!h) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    int rc = rp_traffic_create((rp_sim *)get_external(env, argv[0]), &cfg, &h->t);
+    if (rc != RP_OK) { free(h); return throw_rp(env, rc); }
+    if (napi_create_reference(env, argv[0], 1, &h->sim_ref) != napi_ok ||
+        napi_create_external(env, h, traffic_finalize, NULL, &ext) != napi_ok) {
+        traffic_release(env, h);
+        free(h);
+        napi_throw_error(env, NULL, "N-API call failed");
+        return NULL;
+    }
+    return ext;
+}
+
+static napi_value js_traffic_close(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1];
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    traffic_handle *h = (traffic_handle *)get_external(env, argv[0]);
+    if (h) traffic_release(env, h);
+    return NULL;
+}
+
+/* trafficSubmit(t, Uint32Array entries, Uint32Array keyHashes) -> the id of request 0 */
+static napi_value js_traffic_submit(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 3 || !is_u32(env, argv[1]) || !is_u32(env, argv[2])) {
+        napi_throw_type_error(env, NULL, "entries and key hashes must be Uint32Arrays");
+        return NULL;
+    }
+    size_t ne = 0, nh = 0;
+    const uint32_t *e = opt_u32(env, argv[1], &ne);
+    const uint32_t *k = opt_u32(env, argv[2], &nh);
+    if (ne != nh) {
+        napi_throw_range_error(env, NULL, "entries and key hashes must have one length");
+        return NULL;
+    }
+    rp_traffic *t = get_traffic(env, argv[0]);
+    if (!t) return NULL;
+    uint64_t first = 0;
+    CHECK_RP(rp_traffic_submit(t, e, k, ne, &first));
+    return num(env, (double)first);
+}
+
+/* trafficSubmitUniform(t, seed, first, count); trafficPoll(t); trafficRun(t, k, churn, perRound, seed) */
+static napi_value js_traffic_submit_uniform(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    double seed = 0, first = 0, count = 0;
+    napi_get_value_double(env, argv[1], &seed);
+    napi_get_value_double(env, argv[2], &first);
+    napi_get_value_double(env, argv[3], &count);
+    rp_traffic *t = get_traffic(env, argv[0]);
+    if (!t) return NULL;
+    CHECK_RP(rp_traffic_submit_uniform(t, (uint64_t)seed, (uint64_t)first, (uint64_t)count));
+    return NULL;
+}
+
+static napi_value js_traffic_poll(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1];
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    rp_traffic *t = get_traffic(env, argv[0]);
+    if (!t) return NULL;
+    CHECK_RP(rp_traffic_poll(t));
+    return NULL;
+}
+
+static napi_value js_traffic_run(napi_env env, napi_callback_info info) {
+    size_t argc = 5;
+    napi_value argv[5];
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    int32_t k = 0;
+    bool churn = true;
+    double per = 0, seed = 0;
+    napi_get_value_int32(env, argv[1], &k);
+    napi_get_value_bool(env, argv[2], &churn);
+    napi_get_value_double(env, argv[3], &per);
+    napi_get_value_double(env, argv[4], &seed);
+    rp_traffic *t = get_traffic(env, argv[0]);
+    if (!t) return NULL;
+    CHECK_RP(rp_traffic_run(t, k, churn ? 1 : 0, (uint64_t)per, (uint64_t)seed));
+    return NULL;
+}
+
+/* the reference's event names where it has one (lib/request-proxy/send.js, index.js) */
+static napi_value traffic_stats_obj(napi_env env, const rp_traffic_stats *st) {
+    napi_value o;
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "submitted", num(env, (double)st->submitted));
+    napi_set_named_property(env, o, "local", num(env, (double)st->local));
+    napi_set_named_property(env, o, "delivered", num(env, (double)st->delivered));
+    napi_set_named_property(env, o, "reroutedLocal", num(env, (double)st->rerouted_local));
+    napi_set_named_property(env, o, "failed", num(env, (double)st->failed));
+    napi_set_named_property(env, o, "entryDead", num(env, (double)st->entry_dead));
+    napi_set_named_property(env, o, "requestProxied", num(env, (double)st->proxied));
+    napi_set_named_property(env, o, "sendUnreachable", num(env, (double)st->send_unreachable));
+    napi_set_named_property(env, o, "checksumsDiffer", num(env, (double)st->checksums_differ));
+    napi_set_named_property(env, o, "retryScheduled", num(env, (double)st->retry_scheduled));
+    napi_set_named_property(env, o, "retryAttempted", num(env, (double)st->retry_attempted));
+    napi_set_named_property(env, o, "retryRerouted", num(env, (double)st->retry_rerouted));
+    napi_set_named_property(env, o, "retrySucceeded", num(env, (double)st->retry_succeeded));
+    napi_set_named_property(env, o, "retryFailed", num(env, (double)st->retry_failed));
+    napi_set_named_property(env, o, "misrouted", num(env, (double)st->misrouted));
+    return o;
+}
+
+/* trafficStats(t) -> {stats: {...}, byRetries: Float64Array(45) [outcome * 9 + retries]} */
+static napi_value js_traffic_stats(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1], o;
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    rp_traffic *t = get_traffic(env, argv[0]);
+    if (!t) return NULL;
+    rp_traffic_stats st;
+    uint64_t by[45];
+    CHECK_RP(rp_traffic_read_stats(t, &st, by));
+    void *d;
+    napi_value ba = typed(env, napi_float64_array, 45, 8, &d);
+    for (int i = 0; i < 45; i++) ((double *)d)[i] = (double)by[i];
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "stats", traffic_stats_obj(env, &st));
+    napi_set_named_property(env, o, "byRetries", ba);
+    return o;
+}
+
+/* trafficHistory(t, firstClock, count) -> [ {...} per clock ] */
+static napi_value js_traffic_history(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3], arr;
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    uint32_t first = 0, count = 0;
+    napi_get_value_uint32(env, argv[1], &first);
+    napi_get_value_uint32(env, argv[2], &count);
+    rp_traffic *t = get_traffic(env, argv[0]);
+    if (!t) return NULL;
+    rp_traffic_stats *rows = (rp_traffic_stats *)calloc(count ? count : 1, sizeof *rows);
+    if (!rows) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    int rc = rp_traffic_history(t, first, count, rows);
+    if (rc != RP_OK) { free(rows); return throw_rp(env, rc); }
+    napi_create_array_with_length(env, count, &arr);
+    for (uint32_t i = 0; i < count; i++) napi_set_element(env, arr, i, traffic_stats_obj(env, &rows[i]));
+    free(rows);
+    return arr;
+}
+
+/* trafficPending(t) -> {count, ids: Float64Array, entries, keyHashes: Uint32Array, firstDests: Int32Array,
+ * due, submitClocks, retries: Uint32Array}, in submission order */
+static napi_value js_traffic_pending(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1], o;
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    rp_traffic *t = get_traffic(env, argv[0]);
+    if (!t) return NULL;
+    uint64_t cnt = 0;
+    CHECK_RP(rp_traffic_pending(t, NULL, 0, &cnt));
+    rp_request_pending *p = (rp_request_pending *)calloc(cnt ? cnt : 1, sizeof *p);
+    if (!p) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    int rc = rp_traffic_pending(t, p, cnt, &cnt);
+    if (rc != RP_OK) { free(p); return throw_rp(env, rc); }
+    void *id, *en, *kh, *fd, *du, *sc, *re;
+    napi_value ida = typed(env, napi_float64_array, cnt, 8, &id), ena = typed(env, napi_uint32_array, cnt, 4, &en);
+    napi_value kha = typed(env, napi_uint32_array, cnt, 4, &kh), fda = typed(env, napi_int32_array, cnt, 4, &fd);
+    napi_value dua = typed(env, napi_uint32_array, cnt, 4, &du), sca = typed(env, napi_uint32_array, cnt, 4, &sc);
+    napi_value rea = typed(env, napi_uint32_array, cnt, 4, &re);
+    for (uint64_t i = 0; i < cnt; i++) {
+        ((double *)id)[i] = (double)p[i].id;
+        ((uint32_t *)en)[i] = p[i].entry;
+        ((uint32_t *)kh)[i] = p[i].key_hash;
+        ((int32_t *)fd)[i] = p[i].first_dest;
+        ((uint32_t *)du)[i] = p[i].due;
+        ((uint32_t *)sc)[i] = p[i].submit_clock;
+        ((uint32_t *)re)[i] = p[i].retries;
+    }
+    free(p);
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "count", num(env, (double)cnt));
+    napi_set_named_property(env, o, "ids", ida);
+    napi_set_named_property(env, o, "entries", ena);
+    napi_set_named_property(env, o, "keyHashes", kha);
+    napi_set_named_property(env, o, "firstDests", fda);
+    napi_set_named_property(env, o, "due", dua);
+    napi_set_named_property(env, o, "submitClocks", sca);
+    napi_set_named_property(env, o, "retries", rea);
+    return o;
+}
+
+/* trafficResults(t, firstId, n) -> {dests: Int32Array, outcomes, retries: Uint8Array, submitClocks, doneClocks:
+ * Uint32Array} (track only) */
+static napi_value js_traffic_results(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3], o;
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    double first = 0, nd = 0;
+    napi_get_value_double(env, argv[1], &first);
+    napi_get_value_double(env, argv[2], &nd);
+    rp_traffic *t = get_traffic(env, argv[0]);
+    if (!t) return NULL;
+    if (first < 0 || nd < 0 || nd > 4294967295.0) {
+        napi_throw_range_error(env, NULL, "bad id range");
+        return NULL;
+    }
+    size_t n = (size_t)nd;
+    rp_request_result *r = (rp_request_result *)calloc(n ? n : 1, sizeof *r);
+    if (!r) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    int rc = rp_traffic_results(t, (uint64_t)first, n, r);
+    if (rc != RP_OK) { free(r); return throw_rp(env, rc); }
+    void *de, *oc, *re, *sc, *dc;
+    napi_value dea = typed(env, napi_int32_array, n, 4, &de), oca = typed(env, napi_uint8_array, n, 1, &oc);
+    napi_value rea = typed(env, napi_uint8_array, n, 1, &re), sca = typed(env, napi_uint32_array, n, 4, &sc);
+    napi_value dca = typed(env, napi_uint32_array, n, 4, &dc);
+    for (size_t i = 0; i < n; i++) {
+        ((int32_t *)de)[i] = r[i].dest;
+        ((uint8_t *)oc)[i] = r[i].outcome;
+        ((uint8_t *)re)[i] = r[i].retries;
+        ((uint32_t *)sc)[i] = r[i].submit_clock;
+        ((uint32_t *)dc)[i] = r[i].done_clock;
+    }
+    free(r);
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "dests", dea);
+    napi_set_named_property(env, o, "outcomes", oca);
+    napi_set_named_property(env, o, "retries", rea);
+    napi_set_named_property(env, o, "submitClocks", sca);
+    napi_set_named_property(env, o, "doneClocks", dca);
+    return o;
+}
+
 /* simView(sim, n, node) -> {status: Uint8Array, inc: Float64Array} */
 static napi_value js_sim_view(napi_env env, napi_callback_info info) {
     size_t argc = 3;
@@ -1224,6 +1521,16 @@ static napi_value init(napi_env env, napi_value exports) {
     EXPORT("simChecksums", js_sim_checksums);
     EXPORT("simRingChecksums", js_sim_ring_checksums);
     EXPORT("simRoute", js_sim_route);
+    EXPORT("trafficCreate", js_traffic_create);
+    EXPORT("trafficClose", js_traffic_close);
+    EXPORT("trafficSubmit", js_traffic_submit);
+    EXPORT("trafficSubmitUniform", js_traffic_submit_uniform);
+    EXPORT("trafficPoll", js_traffic_poll);
+    EXPORT("trafficRun", js_traffic_run);
+    EXPORT("trafficStats", js_traffic_stats);
+    EXPORT("trafficHistory", js_traffic_history);
+    EXPORT("trafficPending", js_traffic_pending);
+    EXPORT("trafficResults", js_traffic_results);
     EXPORT("simView", js_sim_view);
     EXPORT("simMembers", js_sim_members);
     EXPORT("simChanges", js_sim_changes);

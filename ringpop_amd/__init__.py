@@ -9,7 +9,7 @@ from ._lib import LIB_PATH, RingpopError, lib  # noqa: F401
 from .farmhash import hash32, hash32_batch  # noqa: F401
 from .hashring import HashRing  # noqa: F401
 from .node import Dissemination, Membership, Node  # noqa: F401
-from .sim import Sim  # noqa: F401
+from .sim import Sim, Traffic  # noqa: F401
 
-__all__ = ["Dissemination", "HashRing", "Membership", "Node", "RingpopError", "Sim", "hash32", "hash32_batch", "lib",
-           "LIB_PATH"]
+__all__ = ["Dissemination", "HashRing", "Membership", "Node", "RingpopError", "Sim", "Traffic", "hash32",
+           "hash32_batch", "lib", "LIB_PATH"]

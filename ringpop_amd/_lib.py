@@ -48,6 +48,35 @@ class RouteStats(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
 
 
+class TrafficConfig(ctypes.Structure):
+    _fields_ = [("max_retries", ctypes.c_int32), ("nschedule", ctypes.c_uint32), ("schedule", ctypes.c_uint32 * 8),
+                ("enforce_consistency", ctypes.c_int32), ("track", ctypes.c_uint32), ("timing", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("capacity", ctypes.c_uint64)]
+
+
+TRAFFIC_STATS = ("submitted", "local", "delivered", "rerouted_local", "failed", "entry_dead", "proxied",
+                 "send_unreachable", "checksums_differ", "retry_scheduled", "retry_attempted", "retry_rerouted",
+                 "retry_succeeded", "retry_failed", "misrouted", "reserved")
+
+
+class TrafficStats(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint64) for k in TRAFFIC_STATS]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+class RequestResult(ctypes.Structure):
+    _fields_ = [("dest", ctypes.c_int32), ("outcome", ctypes.c_uint8), ("retries", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint16), ("submit_clock", ctypes.c_uint32), ("done_clock", ctypes.c_uint32)]
+
+
+class RequestPending(ctypes.Structure):
+    _fields_ = [("id", ctypes.c_uint64), ("entry", ctypes.c_uint32), ("key_hash", ctypes.c_uint32),
+                ("first_dest", ctypes.c_int32), ("due", ctypes.c_uint32), ("submit_clock", ctypes.c_uint32),
+                ("retries", ctypes.c_uint32)]
+
+
 # (name, argtypes) of every entry point declared in include/ringpop_hip.h
 _P = ctypes.c_void_p
 _U8P = ctypes.POINTER(ctypes.c_uint8)
@@ -134,6 +163,17 @@ SIGNATURES = {
     "rp_sim_ring_checksums": ([_P, _P, _SZ], ctypes.c_int),
     "rp_sim_route": ([_P, _P, _P, _SZ, _P, _P, _P, ctypes.POINTER(RouteStats)], ctypes.c_int),
     "rp_sim_route_uniform": ([_P, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(RouteStats)], ctypes.c_int),
+    "rp_traffic_create": ([_P, ctypes.POINTER(TrafficConfig), ctypes.POINTER(_P)], ctypes.c_int),
+    "rp_traffic_destroy": ([_P], ctypes.c_int),
+    "rp_traffic_submit": ([_P, _P, _P, _SZ, _U64P], ctypes.c_int),
+    "rp_traffic_submit_uniform": ([_P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64], ctypes.c_int),
+    "rp_traffic_poll": ([_P], ctypes.c_int),
+    "rp_traffic_run": ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64], ctypes.c_int),
+    "rp_traffic_read_stats": ([_P, ctypes.POINTER(TrafficStats), _P], ctypes.c_int),
+    "rp_traffic_history": ([_P, ctypes.c_uint32, ctypes.c_uint32, _P], ctypes.c_int),
+    "rp_traffic_pending": ([_P, _P, _SZ, _U64P], ctypes.c_int),
+    "rp_traffic_results": ([_P, ctypes.c_uint64, _SZ, _P], ctypes.c_int),
+    "rp_traffic_times": ([_P, _P, _P, _U64P], ctypes.c_int),
     "rp_sim_ping_body": ([_P, ctypes.c_uint32, _P, ctypes.c_uint32, _U32P, _U32P, ctypes.POINTER(ctypes.c_uint64)],
                          ctypes.c_int),
     "rp_sim_handle_ping": ([_P, ctypes.c_uint32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint32, _P, ctypes.c_uint32,

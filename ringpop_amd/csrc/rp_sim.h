@@ -265,4 +265,14 @@ enum {
     STAT_NSTATS
 };
 
+// the partition window separates a from b at S.round; a request from -> to
+// fails (the destination fail-stopped, or the partition between them)
+__device__ inline bool cut(const SimDev& S, uint32_t a, uint32_t b) {
+    return S.part_split > 0 && S.round >= S.part_start && S.round < S.part_end &&
+           ((a < S.part_split) != (b < S.part_split));
+}
+__device__ inline bool unreachable(const SimDev& S, uint32_t from, uint32_t to) {
+    return S.dead[to] || cut(S, from, to);
+}
+
 }  // namespace rp

@@ -3,7 +3,8 @@ import ctypes
 
 import numpy as np
 
-from ._lib import RoundStats, RouteStats, SimConfig, check, lib, ptr
+from ._lib import (RequestPending, RequestResult, RoundStats, RouteStats, SimConfig, TrafficConfig, TrafficStats, check,
+                   lib, ptr)
 
 KERNEL_CATEGORIES = ("churn", "issue", "merge_ping", "merge_resp", "checksum", "other")
 STATUS_NAMES = {0: None, 1: "alive", 2: "suspect", 3: "faulty", 4: "leave"}
@@ -23,6 +24,107 @@ class Loop:
         if self._h:
             lib().rp_loop_destroy(self._h)
             self._h = ctypes.c_void_p()
+
+
+class Traffic:
+    """rp_traffic: requests with the request proxy's retries across rounds
+    (Sim.traffic).  The tracker's clock is its Sim's round
+    count; close it before the Sim (Sim.close does)."""
+
+    OUTCOMES = ("local", "delivered", "rerouted_local", "failed", "entry_dead")
+    PENDING = 255
+    RESULT_DTYPE = np.dtype([("dest", "<i4"), ("outcome", "u1"), ("retries", "u1"), ("reserved", "<u2"),
+                             ("submit_clock", "<u4"), ("done_clock", "<u4")])
+    PENDING_DTYPE = np.dtype([("id", "<u8"), ("entry", "<u4"), ("key_hash", "<u4"), ("first_dest", "<i4"),
+                              ("due", "<u4"), ("submit_clock", "<u4"), ("retries", "<u4")])
+
+    def __init__(self, sim, max_retries=3, schedule=(0, 5, 18), enforce_consistency=True, track=False,
+                 capacity=1 << 20, timing=False):
+        schedule = [int(x) for x in schedule]
+        if not 1 <= len(schedule) <= 8:
+            raise ValueError("traffic: a schedule of 1 to 8 delays")
+        if max_retries < 0:
+            raise ValueError("traffic: max_retries >= 0")
+        cfg = TrafficConfig(max_retries=int(max_retries), nschedule=len(schedule),
+                            enforce_consistency=1 if enforce_consistency else 0, track=1 if track else 0,
+                            timing=1 if timing else 0, capacity=int(capacity))
+        for i, x in enumerate(schedule):
+            cfg.schedule[i] = x
+        self._sim = sim
+        self._h = ctypes.c_void_p()
+        check(lib().rp_traffic_create(sim._h, ctypes.byref(cfg), ctypes.byref(self._h)))
+        sim._traffic.append(self)
+
+    def close(self):
+        if self._h:
+            lib().rp_traffic_destroy(self._h)
+            self._h = ctypes.c_void_p()
+            if self in self._sim._traffic:
+                self._sim._traffic.remove(self)
+
+    def submit(self, entries, key_hashes):
+        """First attempts of request i = (entries[i], key_hashes[i]) now; the id of request 0."""
+        e = np.ascontiguousarray(entries, dtype=np.uint32)
+        h = np.ascontiguousarray(key_hashes, dtype=np.uint32)
+        if e.ndim != 1 or e.shape != h.shape:
+            raise ValueError("submit: two arrays of one length")
+        first = ctypes.c_uint64(0)
+        check(lib().rp_traffic_submit(self._h, ptr(e), ptr(h), len(e), ctypes.byref(first)))
+        return int(first.value)
+
+    def submit_uniform(self, seed, first, count):
+        """Requests first .. first + count - 1 of route_uniform's generator, drawn on the device."""
+        check(lib().rp_traffic_submit_uniform(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), int(count)))
+
+    def poll(self):
+        """Every pending request that is due retries."""
+        check(lib().rp_traffic_poll(self._h))
+
+    def run(self, k, per_round, seed, churn=True):
+        """k times: a round, a poll, a submit_uniform of per_round requests (rp_traffic_run)."""
+        check(lib().rp_traffic_run(self._h, int(k), 1 if churn else 0, int(per_round), int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def stats(self):
+        """(cumulative statistics, by_retries: {outcome: [finals with 0..8 retries]})."""
+        st = TrafficStats()
+        by = np.zeros(45, dtype=np.uint64)
+        check(lib().rp_traffic_read_stats(self._h, ctypes.byref(st), ptr(by)))
+        return st.as_dict(), {k: by[9 * i:9 * i + 9].astype(np.int64).tolist() for i, k in enumerate(self.OUTCOMES)}
+
+    def history(self, first_clock, count):
+        """One statistics dict per clock first_clock .. first_clock + count - 1."""
+        rows = (TrafficStats * max(int(count), 1))()
+        check(lib().rp_traffic_history(self._h, int(first_clock), int(count), rows))
+        return [rows[i].as_dict() for i in range(int(count))]
+
+    def pending_count(self):
+        cnt = ctypes.c_uint64(0)
+        check(lib().rp_traffic_pending(self._h, None, 0, ctypes.byref(cnt)))
+        return int(cnt.value)
+
+    def pending(self):
+        """The pending table in submission order (a PENDING_DTYPE array)."""
+        assert self.PENDING_DTYPE.itemsize == ctypes.sizeof(RequestPending)
+        out = np.zeros(self.pending_count(), dtype=self.PENDING_DTYPE)
+        cnt = ctypes.c_uint64(0)
+        check(lib().rp_traffic_pending(self._h, ptr(out), len(out), ctypes.byref(cnt)))
+        return out[:int(cnt.value)]
+
+    def results(self, first_id, n):
+        """The records of requests first_id .. first_id + n - 1 (track=True; a RESULT_DTYPE array)."""
+        assert self.RESULT_DTYPE.itemsize == ctypes.sizeof(RequestResult)
+        out = np.zeros(int(n), dtype=self.RESULT_DTYPE)
+        check(lib().rp_traffic_results(self._h, int(first_id), len(out), ptr(out)))
+        return out
+
+    def times(self):
+        """timing=True: device ms and calls of the polls and submits, and the peak pending count."""
+        ms = (ctypes.c_double * 2)()
+        calls = (ctypes.c_uint64 * 2)()
+        peak = ctypes.c_uint64(0)
+        check(lib().rp_traffic_times(self._h, ms, calls, ctypes.byref(peak)))
+        return {"poll_ms": ms[0], "polls": int(calls[0]), "submit_ms": ms[1], "submits": int(calls[1]),
+                "peak_pending": int(peak.value)}
 
 
 class Sim:
@@ -56,6 +158,7 @@ class Sim:
                         compact_mul=compact[0] if compact else 0, compact_add=compact[1] if compact else 0,
                         prefix_min=prefix_min, ck_lane_min=ck_lane_min, issue_wave=issue_wave)
         self._h = ctypes.c_void_p()
+        self._traffic = []  # open trackers: closed before the simulation
         self.shards = shards
         if rank is not None and loop is not None:
             check(lib().rp_sim_create_rank_loop(ctypes.byref(cfg), loop._h, rank, ctypes.byref(self._h)))
@@ -132,6 +235,8 @@ class Sim:
 
     def close(self):
         if self._h:
+            for t in list(self._traffic):
+                t.close()
             lib().rp_sim_destroy(self._h)
             self._h = ctypes.c_void_p()
 
@@ -264,6 +369,12 @@ class Sim:
         st = RouteStats()
         check(lib().rp_sim_route_uniform(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(count), ctypes.byref(st)))
         return st.as_dict()
+
+    def traffic(self, **cfg):
+        """A request tracker on this simulation (rp_traffic_create): max_retries=3,
+        schedule=(0, 5, 18) rounds, enforce_consistency=True, track=False,
+        capacity=2**20, timing=False."""
+        return Traffic(self, **cfg)
 
     def address(self, v):
         buf = ctypes.create_string_buffer(64)
