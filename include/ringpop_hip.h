@@ -242,8 +242,9 @@ int rp_sim_exchange_shard_bytes(rp_sim *sim, uint64_t *out, int cap, int *count)
  * node i is the i-th address, so a view indexed by id is in the order
  * generateChecksumString sorts members, lib/membership.js:62-93).  Replaces
  * the 10.x.x.x:300x scheme; every view is re-bootstrapped as rp_sim_create does,
- * so it must come FIRST: after rp_sim_set_views or rp_sim_join it fails with
- * RP_ERR_STATE.  Call order: create, load_addresses, set_views / join, rounds.
+ * so it must come FIRST: after rp_sim_set_views, rp_sim_join, rp_sim_leave or
+ * rp_sim_rejoin it fails with RP_ERR_STATE.  Call order: create,
+ * load_addresses, set_views / join / leave / rejoin, rounds.
  * rp_sim_set_views: re-bootstrap nodes [node_lo, node_lo + count) from
  * views -- status[r * n + a] (0 absent, 1 alive, 2 suspect, 3 faulty, 4 leave) and
  * incarnation[r * n + a] of member a in node node_lo + r's view, its own
@@ -274,6 +275,34 @@ int rp_sim_set_views(rp_sim *sim, uint32_t node_lo, uint32_t count, const int32_
 /* fail-stop `node` at the start of `round` (it stops pinging and answering;
  * requests to it come back as transport errors one wave later) */
 int rp_sim_fail(rp_sim *sim, uint32_t node, uint32_t round);
+/* Graceful leave and rejoin: scheduled events of round
+ * `round` >= the current one, run after the round's joins and before its
+ * churn.  Per node the events alternate leave, rejoin, leave, ... in strictly
+ * increasing rounds, added in that order; anything else is RP_ERR_INVALID.
+ * An event of a node that has fail-stopped or not joined yet is skipped.
+ * Both calls mark the ring checksums stale; in a multi-process cluster every
+ * rank makes the same calls.
+ * rp_sim_leave replaces server/admin-leave-handler.js:30-57:
+ * membership.makeLeave(self, own incarnation) (lib/membership.js:150-152,
+ * 324-352; the update listener takes the node out of its own ring and
+ * records the change, lib/membership-update-listener.js:42-47), gossip.stop()
+ * -- the node pings nobody; it still answers pings and ping-reqs, applies
+ * updates and refutes suspicions of itself -- and suspicion.stopAll()
+ * (lib/swim/suspicion.js:87-108: pending timers cancelled, and no suspect
+ * update starts one until the rejoin, :46-51).  Churn, storms and
+ * rp_round_stats.converged range over nodes that are live and gossiping.
+ * rp_sim_rejoin replaces the rejoin branch of server/admin-join-handler.js:
+ * 36-45: makeAlive(self, now), gossip.start() (one membership.shuffle(),
+ * lib/swim/gossip.js:85) and suspicion.reenable() (lib/swim/suspicion.js:
+ * 30-43).  The node's own status must be leave then: a left node that refuted
+ * a suspicion is alive, the reference would run its join-sender, which is not
+ * modelled -- the next call that reads the simulation returns RP_ERR_STATE. */
+int rp_sim_leave(rp_sim *sim, uint32_t node, uint32_t round);
+int rp_sim_rejoin(rp_sim *sim, uint32_t node, uint32_t round);
+/* bit 0: the node's gossip is stopped (Gossip.isStopped, lib/swim/gossip.js);
+ * bit 1: its suspicion is stopped (Suspicion.isStoppedAll, lib/swim/
+ * suspicion.js:26).  Marks the ring checksums stale. */
+int rp_sim_node_flags(rp_sim *sim, uint32_t node, uint32_t *flags);
 /* requests between ids on different sides of `split` fail during rounds
  * [start, end) (partition injection; split = 0 disables) */
 int rp_sim_partition(rp_sim *sim, uint32_t start, uint32_t end, uint32_t split);

@@ -575,6 +575,12 @@ SimCluster.prototype.fail = function fail(node, round) { addon.simFail(this._sim
 SimCluster.prototype.partition = function partition(start, end, split) {
     addon.simPartition(this._sim, start, end, split);
 };
+// graceful leave and rejoin of `node` at the start of `round` (rp_sim_leave, rp_sim_rejoin:
+// server/admin-leave-handler.js, the rejoin branch of server/admin-join-handler.js); per node they
+// alternate, starting with a leave.  flags(node): {gossipStopped, suspicionStopped}
+SimCluster.prototype.leave = function leave(node, round) { addon.simLeave(this._sim, node, round); };
+SimCluster.prototype.rejoin = function rejoin(node, round) { addon.simRejoin(this._sim, node, round); };
+SimCluster.prototype.flags = function flags(node) { return addon.simFlags(this._sim, node); };
 SimCluster.prototype.round = function round(churn) { return addon.simRound(this._sim, churn !== false); };
 SimCluster.prototype.run = function run(k, churn) { return addon.simRun(this._sim, k, churn !== false); };
 // the same rounds off the event loop (napi_async_work): resolves with the

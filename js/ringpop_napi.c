@@ -493,6 +493,45 @@ static napi_value js_sim_fail(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* simLeave(sim, node, round) -> rp_sim_leave; simRejoin(sim, node, round) -> rp_sim_rejoin (graceful leave and
+ * rejoin at the start of `round`); simFlags(sim, node) -> rp_sim_node_flags as {gossipStopped, suspicionStopped} */
+static napi_value js_sim_leave(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    uint32_t node = 0, round = 0;
+    napi_get_value_uint32(env, argv[1], &node);
+    napi_get_value_uint32(env, argv[2], &round);
+    CHECK_RP(rp_sim_leave((rp_sim *)get_external(env, argv[0]), node, round));
+    return NULL;
+}
+
+static napi_value js_sim_rejoin(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    uint32_t node = 0, round = 0;
+    napi_get_value_uint32(env, argv[1], &node);
+    napi_get_value_uint32(env, argv[2], &round);
+    CHECK_RP(rp_sim_rejoin((rp_sim *)get_external(env, argv[0]), node, round));
+    return NULL;
+}
+
+static napi_value js_sim_flags(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2], o, b;
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    uint32_t node = 0, flags = 0;
+    napi_get_value_uint32(env, argv[1], &node);
+    CHECK_RP(rp_sim_node_flags((rp_sim *)get_external(env, argv[0]), node, &flags));
+    napi_create_object(env, &o);
+    napi_get_boolean(env, (flags & 1u) != 0, &b);
+    napi_set_named_property(env, o, "gossipStopped", b);
+    napi_get_boolean(env, (flags & 2u) != 0, &b);
+    napi_set_named_property(env, o, "suspicionStopped", b);
+    return o;
+}
+
 static napi_value js_sim_partition(napi_env env, napi_callback_info info) {
     size_t argc = 4;
     napi_value argv[4];
@@ -1518,6 +1557,9 @@ static napi_value init(napi_env env, napi_value exports) {
     EXPORT("simJoin", js_sim_join);
     EXPORT("simFail", js_sim_fail);
     EXPORT("simPartition", js_sim_partition);
+    EXPORT("simLeave", js_sim_leave);
+    EXPORT("simRejoin", js_sim_rejoin);
+    EXPORT("simFlags", js_sim_flags);
     EXPORT("simChecksums", js_sim_checksums);
     EXPORT("simRingChecksums", js_sim_ring_checksums);
     EXPORT("simRoute", js_sim_route);

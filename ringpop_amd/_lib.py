@@ -140,6 +140,9 @@ SIGNATURES = {
     "rp_sim_create_rank_loop": ([ctypes.POINTER(SimConfig), _P, ctypes.c_int, ctypes.POINTER(_P)], ctypes.c_int),
     "rp_sim_exchange_shard_bytes": ([_P, _U64P, ctypes.c_int, ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
     "rp_sim_fail": ([_P, ctypes.c_uint32, ctypes.c_uint32], ctypes.c_int),
+    "rp_sim_leave": ([_P, ctypes.c_uint32, ctypes.c_uint32], ctypes.c_int),
+    "rp_sim_rejoin": ([_P, ctypes.c_uint32, ctypes.c_uint32], ctypes.c_int),
+    "rp_sim_node_flags": ([_P, ctypes.c_uint32, _U32P], ctypes.c_int),
     "rp_sim_partition": ([_P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32], ctypes.c_int),
     "rp_sim_storm": ([_P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32], ctypes.c_int),
     "rp_sim_load_addresses": ([_P, _P, _P, ctypes.c_uint32], ctypes.c_int),

@@ -21,6 +21,7 @@ enum : uint32_t {
     SIMERR_PING_FAILED = 1u << 6,
     SIMERR_PREDICATE = 1u << 7,      // internal: a response the predicate proved non-empty was empty
     SIMERR_P2_LIST = 1u << 8,        // internal: a ping-rank receiver list outgrew its launch grid
+    SIMERR_LIFECYCLE = 1u << 9,      // a leave of a node that has left, or a rejoin of one whose own status is not leave
 };
 
 // RESP_LIST_RX: a list (or an expanded fullSync) that arrived from another
@@ -119,6 +120,10 @@ struct SimDev {
     int32_t* npingable;
     uint32_t* mcount;     // members in the node's view (its order row's first mcount entries)
     uint64_t* rng;
+    // n  0 live, 1 fail-stopped, 2 not joined yet; then two more arrays of n
+    // bytes (no fields of their own, so that a run without graceful leaves
+    // passes its kernels the arguments it always did): gossip_off() and
+    // suspicion_off() below
     uint8_t* dead;
     // origins
     Origin* origins;
@@ -271,6 +276,11 @@ __device__ inline bool cut(const SimDev& S, uint32_t a, uint32_t b) {
     return S.part_split > 0 && S.round >= S.part_start && S.round < S.part_end &&
            ((a < S.part_split) != (b < S.part_split));
 }
+// Graceful leave (rp_sim_leave / rp_sim_rejoin; valid on the node's own
+// shard): gossip.stop() ran at node v -- it sends no pings -- and
+// suspicion.stopAll() ran -- suspect updates start no timer there.
+__host__ __device__ inline uint8_t* gossip_off(const SimDev& S) { return S.dead + S.n; }
+__host__ __device__ inline uint8_t* suspicion_off(const SimDev& S) { return S.dead + 2 * (size_t)S.n; }
 __device__ inline bool unreachable(const SimDev& S, uint32_t from, uint32_t to) {
     return S.dead[to] || cut(S, from, to);
 }

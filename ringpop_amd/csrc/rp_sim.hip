@@ -608,7 +608,9 @@ __device__ void wg_splice(const SimDev& S, uint32_t v, uint32_t M, uint32_t J, S
 // (the sender left out entries that were provably no-ops here).
 // JOIN: members absent from the view are taken wholesale and spliced in
 // (wg_splice); without it (the full-view hot kernels of a cluster that has
-// no absent members) such a change is an error.
+// no absent members) such a change is an error.  JOIN also honours a node's
+// stopped suspicion (suspicion_off): runs with graceful leaves take the JOIN
+// kernels, so the full-view instantiations carry no check for it.
 // The node scalars wg_apply's prologue reads (thread 0).  A caller that knows
 // the node before it knows the batch (k_phase3: the node is the block's, the
 // batch comes with the response record) loads them -- and stages the seen
@@ -672,6 +674,9 @@ __device__ uint32_t wg_apply(const SimDev& S, uint32_t v, const Src& src, uint32
         sh.u[3] = (p.dt0 - p.dh) + L > n;
         sh.u[9] = p.rb;
         sh.u[4] = p.dt0; sh.u[8] = p.tt; sh.u[10] = p.ic; sh.u[11] = p.tt != p.th0;
+        // (the JOIN instantiations also run the simulations with graceful
+        // leaves: bit 1 = suspicion.stopAll() ran at v, lib/swim/suspicion.js:46-51)
+        if (JOIN && suspicion_off(S)[v]) sh.u[11] |= 2u;
         sh.ahead = p.dh;
         if (JOIN) sh.a_m0 = p.m0;
     }
@@ -684,7 +689,8 @@ __device__ uint32_t wg_apply(const SimDev& S, uint32_t v, const Src& src, uint32
     uint32_t tail = sh.u[4], ttail = sh.u[8];
     const uint32_t head = sh.ahead;
     const int32_t mark = ring_mark(sh.u[9]);
-    const bool timers_live = sh.u[11] != 0;  // suspicion timers pending at batch start
+    const bool timers_live = JOIN ? (sh.u[11] & 1u) != 0 : sh.u[11] != 0;  // suspicion timers pending at batch start
+    const bool susp_off = JOIN && (sh.u[11] & 2u) != 0;  // suspicion.start refuses: the member just stays suspect
     const uint32_t stamp = (sh.u[10] & STAMP_MASK) << 24;  // count undefined until the next issue
     const SeenWin win = seen_window(S);
     const uint32_t smask = win.smask, olo = win.olo, ohi = win.ohi;
@@ -806,7 +812,7 @@ __device__ uint32_t wg_apply(const SimDev& S, uint32_t v, const Src& src, uint32
             }
             const uint32_t ns = v_status(nv);
             if (ns == ST_SUSPECT) {
-                if (a != v) flags[k] |= 2u;               // suspicion.start (self is skipped)
+                if (a != v && !susp_off) flags[k] |= 2u;  // suspicion.start (self is skipped)
             } else {
                 if (timers_live) ctst[k] = 0;
             }
@@ -2508,6 +2514,10 @@ __device__ inline void seen_clear(const SimDev& S, uint32_t blk) {
 // MembershipIterator.next (lib/membership-iterator.js:29-52): advance to the
 // next pingable member; reaching the end of the list reshuffles it (k_shuffle)
 // and the scan continues from its start.
+// LIFE (runs with graceful leaves): a node whose gossip is stopped picks no
+// target, so it sends nothing this round -- as a receiver, a relay and a
+// ping-req target it goes on as before (server/admin-leave-handler.js:51).
+template <bool LIFE>
 __global__ void k_iterate(SimDev S, uint8_t* need_shuffle, uint32_t* shuf_list, uint32_t* shuf_count) {
     uint32_t v = S.lo + blockIdx.x * blockDim.x + threadIdx.x;
     const bool mine = v < S.lo + S.nl;
@@ -2520,7 +2530,7 @@ __global__ void k_iterate(SimDev S, uint8_t* need_shuffle, uint32_t* shuf_list, 
         S.min_l2[v] = ~0ull;
         S.need_csum[v] = 0;
     }
-    if (mine && !S.dead[v]) {
+    if (mine && !S.dead[v] && !(LIFE && gossip_off(S)[v])) {
         if (S.npingable[v] <= 0) {
             atomicOr(S.err, SIMERR_PING_FAILED);  // "no usable nodes" path not modelled yet
         } else {
@@ -4500,6 +4510,86 @@ __global__ void __launch_bounds__(BLOCK) k_storm(SimDev S, const int32_t* acc, c
     }
 }
 
+// ---------------------------------------------------------------- graceful leave and rejoin
+// DESIGN.md §12.  The round's events, one block per event (ev[b] = node, bit
+// 31: a rejoin), after the joins and before churn.  Each touches its own
+// node's state only, so the blocks are independent.
+//
+// Leave (server/admin-leave-handler.js:30-57): makeLeave(self, own
+// incarnation) -- a local update whose source is the node at its current
+// incarnation (lib/membership.js:150-152, 324-352: a shared local origin, as
+// for k_storm and k_timers); the update listener takes the node out of its
+// own ring ('ringChanged' -> adjustMaxPiggybackCount) and records the change
+// (wg_apply).  Then gossip.stop() (gossip_off: k_iterate picks no target; the
+// iterator's index and round stay as they are) and suspicion.stopAll()
+// (lib/swim/suspicion.js:87-108): every pending timer is cancelled -- the
+// queue's entries [thead, ttail) whose stamp is still the cell's, walked in
+// parallel (live timers name distinct addresses), then thead = ttail -- and
+// suspicion_off makes wg_apply's listener start none until the rejoin.
+//
+// Rejoin (server/admin-join-handler.js:36-45), for a node whose own status is
+// leave (else the reference runs its join-sender, which is not modelled:
+// SIMERR_LIFECYCLE): makeAlive(self, now), source = the node at the leave's
+// incarnation (a local origin again: only churn allocates makeAlive origins);
+// the listener puts it back into its ring.  gossip.start() is one
+// membership.shuffle() on the node's stream (need_shuffle: k_shuffle after
+// this kernel; the iterator continues where it stopped) and
+// suspicion.reenable() clears suspicion_off.  Every shard notes the new incarnation
+// (self_inc: k_churn's origin records on the other shards).
+__global__ void __launch_bounds__(BLOCK) k_lifecycle(SimDev S, const uint32_t* ev, uint64_t now, uint8_t* need_shuffle) {
+    __shared__ Shared sh;
+    const uint32_t v = ev[blockIdx.x] & 0x7FFFFFFFu;
+    const bool rejoin = (ev[blockIdx.x] >> 31) != 0;
+    if (rejoin && threadIdx.x == 0) S.self_inc[v] = now;
+    if (!S.local(v)) return;
+    if (threadIdx.x == 0) {
+        const uint64_t own = S.view[S.row(v) + v].vs;
+        const bool ok = rejoin ? v_status(own) == ST_LEAVE : v_status(own) != ST_LEAVE;
+        sh.u[5] = ok;
+        if (ok) {
+            sh.u[6] = local_origin(S, v, v_inc(own));
+            *S.dangerous = 1;
+            sh.q[1] = rejoin ? pack_view(now, ST_ALIVE) : pack_view(v_inc(own), ST_LEAVE);
+        } else {
+            atomicOr(S.err, SIMERR_LIFECYCLE);
+        }
+    }
+    __syncthreads();
+    if (!sh.u[5]) return;
+    Change c;
+    c.addr = v; c.origin = sh.u[6]; c.vs = sh.q[1];
+    auto src = [&](uint32_t) { return c; };
+    wg_apply(S, v, src, 1, 1, now, 1, 0, sh);
+    if (rejoin) {
+        if (threadIdx.x == 0) { gossip_off(S)[v] = 0; suspicion_off(S)[v] = 0; need_shuffle[v] = 1; }
+        return;
+    }
+    const uint32_t head = S.thead[v], tail = S.ttail[v];
+    const uint32_t m = min(tail - head, S.tcap);  // (a queue past its capacity raised SIMERR_TIMERS_FULL)
+    VEnt* const row = S.view + S.row(v);
+    for (uint32_t i = threadIdx.x; i < m; i += BLOCK) {
+        const uint32_t p = head + i;
+        const uint32_t a = S.tfifo[S.trow(v) + p % S.tcap].x;
+        if (a < S.n && row[a].tstamp == p + 1) row[a].tstamp = 0;
+    }
+    __syncthreads();  // (the queue's bounds were read by every thread)
+    if (threadIdx.x == 0) { S.thead[v] = tail; gossip_off(S)[v] = 1; suspicion_off(S)[v] = 1; }
+}
+
+// node v's pending suspicion timers: the queue entries whose stamp is still
+// the cell's (k_timers' liveness rule); one block
+__global__ void __launch_bounds__(256) k_timer_count(SimDev S, uint32_t v, uint32_t* out) {
+    const uint32_t head = S.thead[v], tail = S.ttail[v];
+    const uint32_t m = min(tail - head, S.tcap);
+    uint32_t c = 0;
+    for (uint32_t i = threadIdx.x; i < m; i += 256) {
+        const uint32_t p = head + i;
+        const uint32_t a = S.tfifo[S.trow(v) + p % S.tcap].x;
+        c += a < S.n && S.view[S.row(v) + a].tstamp == p + 1;
+    }
+    if (c) atomicAdd(out, c);
+}
+
 // ---------------------------------------------------------------- join path
 // SURVEY.md §8(f)4; DESIGN.md §3.  A node outside the cluster (dead = 2: no
 // view, not pinging, unknown to the others) joins at the start of a round,
@@ -4812,12 +4902,15 @@ __global__ void k_mark_dead(SimDev S, const int32_t* ids, uint32_t k) {
 // its last block, behind a device-scope fence per block, cost 128 us per
 // round on gfx950 -- each fence writes back the XCD's L2 -- so a single shard
 // still finishes in k_converge_done.)
+// LIFE: a node that left gracefully pings nobody and its view goes stale by
+// design: convergence is taken over the nodes that are live and gossiping.
+template <bool LIFE>
 __global__ void __launch_bounds__(BLOCK) k_round_end(SimDev S, unsigned long long* fp_mm, uint32_t ncv) {
     __shared__ BlockScratch sc;
     if (blockIdx.x < ncv) {
         uint64_t lo = ~0ull, hi = 0;
         for (uint32_t v = S.lo + blockIdx.x * BLOCK + threadIdx.x; v < S.lo + S.nl; v += ncv * BLOCK) {
-            if (S.dead[v]) continue;
+            if (S.dead[v] || (LIFE && gossip_off(S)[v])) continue;
             const uint64_t f = S.fp[v];
             lo = f < lo ? f : lo;
             hi = f > hi ? f : hi;
@@ -5955,6 +6048,8 @@ struct Shard {
     unsigned long long* h_xrow = nullptr;  // pinned: G x 2 x G response payload counts (words, escapes)
     uint32_t npts = 0, ncoll = 0, seen_words = 0;
     bool join_mode = false;  // views may lack members: the JOIN merge kernels
+    bool life_mode = false;  // graceful leaves scheduled (with join_mode): k_iterate / k_round_end skip gossip-off nodes
+    DevBuf<uint32_t> life_ev, tcount;  // a round's events (k_lifecycle); k_timer_count's result
     bool fault_mode = false;  // fail-stops, storms or partitions scheduled: the settled-filter issue kernels
     bool issue_wave = RP_ISSUE_WAVE != 0;  // rp_sim_config.issue_wave: the one-wave issue kernels where eligible
     // k_phase1 / k_p2_respond as one wave per node (wave_issue): runs without
@@ -6308,7 +6403,9 @@ void Shard::setup() {
     RP_HIP(hipMemcpyAsync(cmem_off.p, h_cmem_off.data(), (ncoll + 1) * 4, hipMemcpyHostToDevice, st));
     if (!h_cmem.empty()) RP_HIP(hipMemcpyAsync(cmem.p, h_cmem.data(), h_cmem.size() * 4, hipMemcpyHostToDevice, st));
     fp.alloc(n); csum.alloc(n); csum_valid.alloc(n); iter_index.alloc(n); iter_round.alloc(n); npingable.alloc(n); mcount.alloc(n);
-    rng.alloc(n); dead.alloc(n);
+    rng.alloc(n); dead.alloc(3 * (size_t)n);  // (+ gossip_off, suspicion_off)
+    RP_HIP(hipMemsetAsync(dead.p, 0, 3 * (size_t)n, st));
+    tcount.alloc(1);
     // (table slots stay below ORIGIN_ID_MASK, the log's tombstone id)
     uint32_t ocap = cfg.origin_slots ? cfg.origin_slots : rp::ORIGIN_ID_MASK;
     if (ocap > rp::ORIGIN_ID_MASK) throw Error(RP_ERR_INVALID, "origin_slots must be < 2^23");
@@ -6743,8 +6840,12 @@ void Shard::stage_churn(bool churn_active, uint32_t slot, uint32_t storm_k, uint
 void Shard::stage_issue() {
     using namespace rp;
     timed(1, [&] {
-        hipLaunchKernelGGL(k_iterate, dim3(grid_for(nl, 64)), dim3(64), 0, st, d, need_shuffle.p, shuf_list.p,
-                           shuf_count.p);
+        if (life_mode)
+            hipLaunchKernelGGL(k_iterate<true>, dim3(grid_for(nl, 64)), dim3(64), 0, st, d, need_shuffle.p, shuf_list.p,
+                               shuf_count.p);
+        else
+            hipLaunchKernelGGL(k_iterate<false>, dim3(grid_for(nl, 64)), dim3(64), 0, st, d, need_shuffle.p, shuf_list.p,
+                               shuf_count.p);
         // (a block holds the n * 2 bytes of LDS, one per CU at 65,536 nodes;
         // iterators wrap once per view length, a few nodes a round: a small
         // grid strides over them and leaves the CUs to the other shards' work)
@@ -6914,7 +7015,8 @@ void Shard::stage_end() {
     using namespace rp;
     timed(5, [&] {
         const uint32_t ncv = grid_for(nl, BLOCK * 4);
-        hipLaunchKernelGGL(k_round_end, dim3(ncv + 64 * STAT_NSTATS), dim3(BLOCK), 0, st, d, fp_mm.p, ncv);
+        if (life_mode) hipLaunchKernelGGL(k_round_end<true>, dim3(ncv + 64 * STAT_NSTATS), dim3(BLOCK), 0, st, d, fp_mm.p, ncv);
+        else hipLaunchKernelGGL(k_round_end<false>, dim3(ncv + 64 * STAT_NSTATS), dim3(BLOCK), 0, st, d, fp_mm.p, ncv);
         if (G == 1)
             hipLaunchKernelGGL(k_converge_done, dim3(1), dim3(64), 0, st, d, (const unsigned long long*)fp_mm.p,
                                totals.p);
@@ -7176,10 +7278,30 @@ struct rp_sim {
     struct JoinEv { uint32_t round, joiner; std::vector<int32_t> seeds; };
     std::vector<JoinEv> joins;               // rp_sim_join's schedule, in order
     std::vector<int32_t> join_round;         // per node: round it joins at, -1 = a member from the start
-    bool live_at(uint32_t i, uint32_t r) const {  // neither failed nor still outside the cluster at round r
-        return (fail_round[i] < 0 || (uint32_t)fail_round[i] > r) && (join_round[i] < 0 || (uint32_t)join_round[i] <= r);
+    // rp_sim_leave / rp_sim_rejoin: per node the rounds of its events, strictly
+    // increasing, leave (even index) and rejoin (odd) in turn; by round, the
+    // events (node, bit 31: a rejoin) in call order
+    std::vector<std::vector<uint32_t>> life;
+    std::map<uint32_t, std::vector<uint32_t>> life_at;
+    // the node's gossip runs during round r: a function of the schedule, like
+    // live_at (an event before the node's join is skipped)
+    bool gossiping_at(uint32_t i, uint32_t r) const {
+        if (life.empty()) return true;
+        bool on = true;
+        const std::vector<uint32_t>& e = life[i];
+        for (size_t j = 0; j < e.size() && e[j] <= r; j++)
+            if (join_round[i] < 0 || e[j] >= (uint32_t)join_round[i]) on = (j & 1) != 0;
+        return on;
     }
+    // neither failed nor still outside the cluster at round r, and gossiping:
+    // the nodes churn and storms draw from
+    bool live_at(uint32_t i, uint32_t r) const {
+        return (fail_round[i] < 0 || (uint32_t)fail_round[i] > r) && (join_round[i] < 0 || (uint32_t)join_round[i] <= r) &&
+               gossiping_at(i, r);
+    }
+    void schedule_life(uint32_t node, uint32_t r, bool rejoin);
     void join_step(uint32_t r, uint64_t now);
+    void life_step(uint32_t r, uint64_t now);
     bool faults = false;
     bool views_set = false;                  // rp_sim_set_views ran (rp_sim_load_addresses must come first)
     uint32_t part[3] = {0, 0, 0};
@@ -7641,6 +7763,60 @@ void rp_sim::join_step(uint32_t r, uint64_t now) {
     }
 }
 
+// The round's graceful leaves and rejoins (rp_sim_leave / rp_sim_rejoin;
+// k_lifecycle).  Every shard stages the same list; an event of a node that has
+// fail-stopped or has not joined yet is skipped.
+void rp_sim::life_step(uint32_t r, uint64_t now) {
+    using namespace rp;
+    const auto it = life_at.find(r);
+    if (it == life_at.end()) return;
+    std::vector<uint32_t> ev;
+    bool any_rejoin = false;
+    for (uint32_t e : it->second) {
+        const uint32_t v = e & 0x7FFFFFFFu;
+        if (fail_round[v] >= 0 && (uint32_t)fail_round[v] <= r) continue;
+        if (join_round[v] >= 0 && (uint32_t)join_round[v] > r) continue;
+        ev.push_back(e);
+        any_rejoin |= (e >> 31) != 0;
+    }
+    if (ev.empty()) return;
+    const uint32_t E = (uint32_t)ev.size();
+    for (auto& s : sh) {
+        s->life_ev.reserve(E);
+        RP_HIP(hipMemcpyAsync(s->life_ev.p, ev.data(), (size_t)E * 4, hipMemcpyHostToDevice, s->st));
+        RP_HIP(hipStreamSynchronize(s->st));  // (ev is a host temporary)
+        s->timed(0, [&] {
+            hipLaunchKernelGGL(k_lifecycle, dim3(E), dim3(BLOCK), 0, s->st, s->d, (const uint32_t*)s->life_ev.p, now,
+                               s->need_shuffle.p);
+            if (any_rejoin)  // gossip.start() -> shuffle(); the iterator keeps its index
+                hipLaunchKernelGGL(k_shuffle, dim3(std::min<uint32_t>(s->nl, 2048)), dim3(BLOCK), (size_t)n * 2, s->st, s->d,
+                                   s->need_shuffle.p, 0, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
+        });
+    }
+}
+
+// rp_sim_leave / rp_sim_rejoin: the schedule's rules, then what
+// a run with such events needs: the fault stages (local origins set
+// `dangerous`), the JOIN merge kernels (they honour a stopped suspicion) and
+// no bound on the members a ring can lose (a leave shrinks rings without any
+// node declaring a member faulty: k_need_checksums, k_pr_need).
+void rp_sim::schedule_life(uint32_t node, uint32_t r, bool rejoin) {
+    if (node >= n) throw Error(RP_ERR_INVALID, "bad node");
+    if (r < round) throw Error(RP_ERR_INVALID, "round already simulated");
+    if (r > (1u << 30)) throw Error(RP_ERR_INVALID, "round out of range");
+    if (life.empty()) life.resize(n);
+    std::vector<uint32_t>& e = life[node];
+    if (((e.size() & 1) != 0) != rejoin)
+        throw Error(RP_ERR_INVALID, rejoin ? "a rejoin follows a leave of the same node" : "the node has a leave without a rejoin");
+    if (!e.empty() && r <= e.back()) throw Error(RP_ERR_INVALID, "a node's events come in strictly increasing rounds");
+    e.push_back(r);
+    life_at[r].push_back(node | (rejoin ? 0x80000000u : 0u));
+    ring_csum_stale = true;
+    faults = true;
+    for (auto& s : sh) { s->join_mode = true; s->life_mode = true; s->faulty_unbounded = true; }
+    presize_exchange();
+}
+
 void rp_sim::enqueue_round(bool churn_active, uint32_t slot) {
     using namespace rp;
     const uint64_t now = T0 + PERIOD_MS * round;
@@ -7657,6 +7833,7 @@ void rp_sim::enqueue_round(bool churn_active, uint32_t slot) {
     for (auto& s : sh) s->fault_mode = faults || part[1] > part[0];
     each([&](Shard& sr) { Shard* const s = &sr; s->stage_start(round, churn_active, slot, dead_now, faults, part, sk); });
     join_step(round, now);
+    if (!life_at.empty()) life_step(round, now);
     each([&](Shard& sr) { Shard* const s = &sr; s->stage_churn(churn_active, slot, sk, now); });
     each([&](Shard& sr) { Shard* const s = &sr; s->stage_issue(); });
     if (G > 1) {
@@ -7937,10 +8114,13 @@ void rp_sim::check_errors() {
     if (e & rp::SIMERR_PING_FAILED) m += " a node has no pingable member (not modelled on device);";
     if (e & rp::SIMERR_PREDICATE) m += " internal: checksum-snapshot predicate violated;";
     if (e & rp::SIMERR_P2_LIST) m += " internal: a ping-rank receiver list outgrew its launch grid;";
+    if (e & rp::SIMERR_LIFECYCLE)
+        m += " a leave of a node that had left, or a rejoin of a node whose own status was not leave (the join-sender"
+             " is not modelled);";
     int code = (e & (rp::SIMERR_ORIGIN_FULL | rp::SIMERR_ARENA_FULL | rp::SIMERR_SNAP_FULL | rp::SIMERR_RINGOPS |
                      rp::SIMERR_TIMERS_FULL))
                    ? RP_ERR_CAPACITY
-                   : RP_ERR_UNSUPPORTED;
+                   : (e & rp::SIMERR_LIFECYCLE) ? RP_ERR_STATE : RP_ERR_UNSUPPORTED;
     throw Error(code, m);
 }
 
@@ -8157,6 +8337,37 @@ int rp_sim_fail(rp_sim* s, uint32_t node, uint32_t round) {
     });
 }
 
+int rp_sim_leave(rp_sim* s, uint32_t node, uint32_t round) {
+    return rp::guarded([&] {
+        if (!s) throw Error(RP_ERR_INVALID, "null sim");
+        RP_HIP(hipSetDevice(s->dev));
+        s->schedule_life(node, round, false);
+    });
+}
+
+int rp_sim_rejoin(rp_sim* s, uint32_t node, uint32_t round) {
+    return rp::guarded([&] {
+        if (!s) throw Error(RP_ERR_INVALID, "null sim");
+        RP_HIP(hipSetDevice(s->dev));
+        s->schedule_life(node, round, true);
+    });
+}
+
+int rp_sim_node_flags(rp_sim* c, uint32_t node, uint32_t* flags) {
+    return rp::guarded([&] {
+        if (!c || node >= c->n || !flags) throw Error(RP_ERR_INVALID, "bad argument");
+        RP_HIP(hipSetDevice(c->dev));
+        c->ring_csum_stale = true;
+        c->check_errors();
+        Shard* s = &c->owner_of(node);
+        uint8_t g = 0, q = 0;
+        RP_HIP(hipMemcpyAsync(&g, rp::gossip_off(s->d) + node, 1, hipMemcpyDeviceToHost, s->st));
+        RP_HIP(hipMemcpyAsync(&q, rp::suspicion_off(s->d) + node, 1, hipMemcpyDeviceToHost, s->st));
+        RP_HIP(hipStreamSynchronize(s->st));
+        *flags = (g ? 1u : 0u) | (q ? 2u : 0u);
+    });
+}
+
 // Arbitrary clusters: the cluster's addresses, then the
 // full-view set() bootstrap from given views.  Both before the first round;
 // in a multi-process cluster every rank makes the same calls.
@@ -8167,8 +8378,9 @@ int rp_sim_load_addresses(rp_sim* s, const uint8_t* bytes, const uint64_t* off, 
         if (n != s->n) throw Error(RP_ERR_INVALID, "address count differs from the cluster size");
         // the shards are rebuilt from scratch (full views): views or a join
         // schedule set before would be silently dropped
-        if (s->views_set || !s->joins.empty())
-            throw Error(RP_ERR_STATE, "addresses must be loaded before rp_sim_set_views / rp_sim_join");
+        if (s->views_set || !s->joins.empty() || !s->life.empty())
+            throw Error(RP_ERR_STATE,
+                        "addresses must be loaded before rp_sim_set_views / rp_sim_join / rp_sim_leave / rp_sim_rejoin");
         // (new shards, new points: the routing tables go with the old ones)
         s->ring_csum_stale = true;
         s->route_tab.release();
@@ -8685,6 +8897,10 @@ int rp_sim_node_info(rp_sim* c, uint32_t node, int64_t* info) {
         RP_HIP(hipMemcpyAsync(&dd, s->dead.p + node, 1, hipMemcpyDeviceToHost, s->st));
         RP_HIP(hipMemcpyAsync(&rs, s->rng.p + node, 8, hipMemcpyDeviceToHost, s->st));
         RP_HIP(hipMemcpyAsync(inr.data(), s->in_ring.p + s->d.row(node), s->n, hipMemcpyDeviceToHost, s->st));
+        uint32_t tc = 0;
+        RP_HIP(hipMemsetAsync(s->tcount.p, 0, 4, s->st));
+        hipLaunchKernelGGL(rp::k_timer_count, dim3(1), dim3(256), 0, s->st, s->d, node, s->tcount.p);
+        RP_HIP(hipMemcpyAsync(&tc, s->tcount.p, 4, hipMemcpyDeviceToHost, s->st));
         RP_HIP(hipStreamSynchronize(s->st));
         // ring checksum: hash32(sorted server names joined by ';') (lib/ring.js:96-105)
         std::string str;
@@ -8697,7 +8913,7 @@ int rp_sim_node_info(rp_sim* c, uint32_t node, int64_t* info) {
         int e = rp_hash32((const uint8_t*)str.data(), str.size(), &rcs);
         if (e) throw Error(e, rp_last_error());
         info[0] = mpb; info[1] = rc; info[2] = rcs; info[3] = ii; info[4] = ir; info[5] = dd;
-        info[6] = (int64_t)rs; info[7] = 0;
+        info[6] = (int64_t)rs; info[7] = tc;
     });
 }
 

@@ -131,7 +131,7 @@ class Sim:
     def __init__(self, n, seed, churn_k=None, arena_entries=0, snapshot_slots=0, origin_slots=0, failures=None,
                  partition=None, seen_window=0, replica_hash_shift=0, shards=1, rank=None, unique_id=None,
                  storm=None, addresses=None, views=None, joins=None, compact=None, loop=None, prefix_min=0, ck_lane_min=0,
-                 issue_wave=0):
+                 issue_wave=0, leaves=None, rejoins=None):
         """shards > 1: the nodes are split into `shards` shards.  With rank=None
         all shards run in this process (rp_sim_create_shards); with a rank, this
         process holds that shard of a one-process-per-GPU cluster whose RCCL
@@ -142,6 +142,8 @@ class Sim:
         (rp_sim_load_addresses); views: (status, incarnation) arrays of shape
         (n, n) for the bootstrap (rp_sim_set_views; status 0 = absent);
         joins: [(round, joiner, [seeds...]), ...] (rp_sim_join);
+        leaves, rejoins: {round: [ids]} graceful leaves and rejoins (rp_sim_leave,
+        rp_sim_rejoin; per node they alternate, starting with a leave);
         compact: (mul, add) log-compaction thresholds (testing; None = auto);
         prefix_min: the window shrink that triggers the issue's head packing
         beyond the entries it moves (testing; 0 = auto, 512);
@@ -182,6 +184,27 @@ class Sim:
             self.join(joins)
         if views is not None:
             self.set_views(views[0], views[1])
+        # (per node in round order, as the schedule's rules ask; a round's leaves first)
+        events = [(int(r), 0, int(v)) for r, ids in (leaves or {}).items() for v in ids]
+        events += [(int(r), 1, int(v)) for r, ids in (rejoins or {}).items() for v in ids]
+        for rnd, kind, v in sorted(events):
+            (self.rejoin if kind else self.leave)(v, rnd)
+
+    def leave(self, node, round):
+        """rp_sim_leave: `node` leaves gracefully at the start of `round` (>= the
+        current one): makeLeave(self), gossip.stop(), suspicion.stopAll()."""
+        check(lib().rp_sim_leave(self._h, int(node), int(round)))
+
+    def rejoin(self, node, round):
+        """rp_sim_rejoin: a node that left rejoins at the start of `round`:
+        makeAlive(self, now), gossip.start(), suspicion.reenable()."""
+        check(lib().rp_sim_rejoin(self._h, int(node), int(round)))
+
+    def flags(self, v):
+        """rp_sim_node_flags: {"gossip_stopped", "suspicion_stopped"} of node v."""
+        f = ctypes.c_uint32(0)
+        check(lib().rp_sim_node_flags(self._h, int(v), ctypes.byref(f)))
+        return {"gossip_stopped": bool(f.value & 1), "suspicion_stopped": bool(f.value & 2)}
 
     def join(self, joins):
         """rp_sim_join: [(round, joiner, [seed, ...]), ...] in processing order."""
