@@ -433,6 +433,45 @@ int rp_sim_route(rp_sim *sim, const uint32_t *entries, const uint32_t *key_hashe
                  uint8_t *outcomes, uint8_t *owner_agrees, rp_route_stats *stats);
 int rp_sim_route_uniform(rp_sim *sim, uint64_t seed, uint64_t count, rp_route_stats *stats);
 
+/* ---- Ownership census (between rounds) ---------------------------------------
+ * For the whole 2^32 hash space, how many live nodes believe they own a key
+ * (DESIGN.md §13).  Node v is a claimant iff it is neither fail-stopped nor
+ * still outside the cluster (rp_sim_node_info's dead == 0; a node that left
+ * gracefully is one, and its ring, which lacks itself, claims nothing).  v
+ * claims hash h iff HashRing.lookup(h) in v's own view is v (index.js:409-423,
+ * handleOrProxy's dest === whoami() test, :607-634), or v's ring is empty
+ * (lookup falls back to whoami: rp_sim_route's LOCAL rule).
+ *
+ * The sorted distinct replica hashes pt_hash[0 .. intervals) of all n servers
+ * cut the hash space into `intervals` intervals: interval i >= 1 is
+ * (pt_hash[i-1], pt_hash[i]], interval 0 is the wrap -- the hashes above the
+ * last point and up to the first.  Every view's lookup is constant on an
+ * interval; claims(i) is the number of claimants that claim it.
+ *
+ * rp_sim_ownership: measure[k] is the number of hashes with exactly k
+ * claimants (k < 7; measure[7]: 7 or more; the eight sum to 2^32);
+ * max_claims the largest claims(i) and max_claims_hash the pt_hash[i] of the
+ * first interval (lowest i) that reaches it.  claimed (NULL, or cap >= n
+ * entries) gets per node the number of hashes it claims: 0 for a node that is
+ * no claimant, 2^32 for an empty ring or a ring of the node alone.
+ *
+ * rp_sim_ownership_at: claims[j] = claims(i) of the interval key_hashes[j]
+ * falls in (the first point >= the hash, else interval 0).
+ *
+ * Both are exact, computed on the device in time proportional to the ring's
+ * points, and cached like the ring checksums: a second call without a call
+ * that can change a ring in between only copies.  Like a route they need every
+ * node's view on this process's device: RP_ERR_UNSUPPORTED on one rank of a
+ * multi-process or loop cluster; in-process shards give the one-shard results.
+ * A claimed buffer with cap < n is RP_ERR_INVALID before any state changes. */
+typedef struct {
+    uint64_t measure[8];
+    uint64_t claimants, intervals, max_claims, max_claims_hash;
+    uint64_t reserved[4];
+} rp_ownership_stats;
+int rp_sim_ownership(rp_sim *sim, rp_ownership_stats *stats, uint64_t *claimed, size_t cap);
+int rp_sim_ownership_at(rp_sim *sim, const uint32_t *key_hashes, size_t n, uint32_t *claims);
+
 /* ---- Request traffic with proxy retries across rounds ------------------------
  * Replaces the RequestProxySend state machine (lib/request-proxy/send.js) for
  * batches of single-key requests that live across rounds: a tracker keeps a

@@ -607,6 +607,15 @@ SimCluster.ROUTE_OUTCOMES = ['local', 'delivered', 'checksumsDiffer', 'unreachab
 SimCluster.prototype.route = function route(entries, keyHashes) {
     return addon.simRoute(this._sim, entries, keyHashes);
 };
+// The ownership census (rp_sim_ownership): over the whole 2^32 hash space, how
+// many live instances claim a key in their own view.  {measure: hashes with
+// exactly 0..6 claimants ([7]: 7 or more), claimants, intervals, maxClaims,
+// maxClaimsHash, claimed: BigUint64Array of the hashes each instance claims}
+SimCluster.prototype.ownership = function ownership() { return addon.simOwnership(this._sim); };
+// the number of live instances that claim each key hash (a Uint32Array)
+SimCluster.prototype.ownershipAt = function ownershipAt(keyHashes) {
+    return addon.simOwnershipAt(this._sim, keyHashes);
+};
 // Request traffic with the request proxy's retries across rounds
 // (rp_traffic_*; lib/request-proxy/send.js): opts {maxRetries: 3, schedule:
 // [0, 5, 18] rounds, enforceConsistency: true, track: false, capacity: 2^20}.

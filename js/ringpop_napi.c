@@ -620,6 +620,50 @@ static napi_value js_sim_route(napi_env env, napi_callback_info info) {
     return o;
 }
 
+/* simOwnership(sim) -> {measure: [8], claimants, intervals, maxClaims, maxClaimsHash,
+ * claimed: BigUint64Array} (rp_sim_ownership) */
+static napi_value js_sim_ownership(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1], o, m;
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    rp_sim *sim;
+    uint32_t n;
+    CHECK_RP(sim_size(env, argv[0], &sim, &n));
+    void *cl;
+    napi_value ca = typed(env, napi_biguint64_array, (size_t)n, 8, &cl);
+    rp_ownership_stats st;
+    memset(&st, 0, sizeof st);
+    CHECK_RP(rp_sim_ownership(sim, &st, (uint64_t *)cl, n));
+    napi_create_array_with_length(env, 8, &m);
+    for (uint32_t k = 0; k < 8; k++) napi_set_element(env, m, k, num(env, (double)st.measure[k]));
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "measure", m);
+    napi_set_named_property(env, o, "claimants", num(env, (double)st.claimants));
+    napi_set_named_property(env, o, "intervals", num(env, (double)st.intervals));
+    napi_set_named_property(env, o, "maxClaims", num(env, (double)st.max_claims));
+    napi_set_named_property(env, o, "maxClaimsHash", num(env, (double)st.max_claims_hash));
+    napi_set_named_property(env, o, "claimed", ca);
+    return o;
+}
+
+/* simOwnershipAt(sim, Uint32Array keyHashes) -> Uint32Array (rp_sim_ownership_at) */
+static napi_value js_sim_ownership_at(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2];
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    rp_sim *sim = (rp_sim *)get_external(env, argv[0]);
+    if (argc < 2 || !is_u32(env, argv[1])) {
+        napi_throw_type_error(env, NULL, "key hashes must be a Uint32Array");
+        return NULL;
+    }
+    size_t nh = 0;
+    const uint32_t *h = opt_u32(env, argv[1], &nh);
+    void *out;
+    napi_value ta = typed(env, napi_uint32_array, nh, 4, &out);
+    CHECK_RP(rp_sim_ownership_at(sim, h, nh, (uint32_t *)out));
+    return ta;
+}
+
 /* ---- request traffic with proxy retries (rp_traffic_*): a tracker handle keeps
  * its simulation's handle alive until it is closed or collected */
 typedef struct {
@@ -1563,6 +1607,8 @@ static napi_value init(napi_env env, napi_value exports) {
     EXPORT("simChecksums", js_sim_checksums);
     EXPORT("simRingChecksums", js_sim_ring_checksums);
     EXPORT("simRoute", js_sim_route);
+    EXPORT("simOwnership", js_sim_ownership);
+    EXPORT("simOwnershipAt", js_sim_ownership_at);
     EXPORT("trafficCreate", js_traffic_create);
     EXPORT("trafficClose", js_traffic_close);
     EXPORT("trafficSubmit", js_traffic_submit);

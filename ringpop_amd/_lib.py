@@ -48,6 +48,16 @@ class RouteStats(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
 
 
+class OwnershipStats(ctypes.Structure):
+    _fields_ = [("measure", ctypes.c_uint64 * 8), ("claimants", ctypes.c_uint64), ("intervals", ctypes.c_uint64),
+                ("max_claims", ctypes.c_uint64), ("max_claims_hash", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 4)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in ("claimants", "intervals", "max_claims", "max_claims_hash")}
+        d["measure"] = [int(x) for x in self.measure]
+        return d
+
+
 class TrafficConfig(ctypes.Structure):
     _fields_ = [("max_retries", ctypes.c_int32), ("nschedule", ctypes.c_uint32), ("schedule", ctypes.c_uint32 * 8),
                 ("enforce_consistency", ctypes.c_int32), ("track", ctypes.c_uint32), ("timing", ctypes.c_uint32),
@@ -166,6 +176,8 @@ SIGNATURES = {
     "rp_sim_ring_checksums": ([_P, _P, _SZ], ctypes.c_int),
     "rp_sim_route": ([_P, _P, _P, _SZ, _P, _P, _P, ctypes.POINTER(RouteStats)], ctypes.c_int),
     "rp_sim_route_uniform": ([_P, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(RouteStats)], ctypes.c_int),
+    "rp_sim_ownership": ([_P, ctypes.POINTER(OwnershipStats), _P, _SZ], ctypes.c_int),
+    "rp_sim_ownership_at": ([_P, _P, _SZ, _P], ctypes.c_int),
     "rp_traffic_create": ([_P, ctypes.POINTER(TrafficConfig), ctypes.POINTER(_P)], ctypes.c_int),
     "rp_traffic_destroy": ([_P], ctypes.c_int),
     "rp_traffic_submit": ([_P, _P, _P, _SZ, _U64P], ctypes.c_int),

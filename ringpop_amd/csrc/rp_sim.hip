@@ -5933,6 +5933,7 @@ __global__ void __launch_bounds__(256) k_route(SimDev S, const RouteShard* tab, 
 #include <memory>
 
 #include "rp_internal.h"
+#include "rp_own.h"
 
 namespace {
 
@@ -7325,7 +7326,20 @@ struct rp_sim {
     DevBuf<uint32_t> route_dir;
     uint32_t route_dir_shift = 32;
     void refresh_ring_checksums();
-    void route_prepare();
+    void route_prepare(bool checksums = true);
+    // ownership census (rp_sim_ownership / rp_sim_ownership_at; DESIGN.md
+    // §13): the same cache rule with a flag of its own -- the counts per
+    // interval, per node and the stats stay until an entry point that can
+    // change a ring ran.  The server -> point index and the shards' dead
+    // arrays are built on first use and dropped with the shards.
+    bool own_stale = true;
+    DevBuf<uint32_t> own_srv_pt, own_claims;
+    DevBuf<int32_t> own_diff, own_tile;
+    DevBuf<unsigned long long> own_claimed, own_out;
+    DevBuf<const uint8_t*> own_dead;
+    rp_ownership_stats own_stats{};
+    rp::OwnArgs own_args();
+    void own_refresh();
     template <bool UNIFORM>
     void route_launch(const uint32_t* entries, const uint32_t* keys, uint64_t seed, uint64_t count, int32_t* dests,
                       uint8_t* outcomes, uint8_t* agrees, rp_route_stats* stats);
@@ -7812,6 +7826,7 @@ void rp_sim::schedule_life(uint32_t node, uint32_t r, bool rejoin) {
     e.push_back(r);
     life_at[r].push_back(node | (rejoin ? 0x80000000u : 0u));
     ring_csum_stale = true;
+    own_stale = true;
     faults = true;
     for (auto& s : sh) { s->join_mode = true; s->life_mode = true; s->faulty_unbounded = true; }
     presize_exchange();
@@ -8036,13 +8051,19 @@ void rp_sim::refresh_ring_checksums() {
 
 // What a route needs besides the simulation state: fresh ring checksums, the
 // shards' base pointers and the bucket directory (about one point per bucket).
-void rp_sim::route_prepare() {
+void rp_sim::route_prepare(bool checksums) {
     if (comm)
         throw Error(RP_ERR_UNSUPPORTED, "routing needs every node's view: not available on one rank of a multi-process "
                                         "or loop cluster");
     RP_HIP(hipSetDevice(dev));
     check_errors();
-    refresh_ring_checksums();
+    if (checksums) refresh_ring_checksums();
+    // (the census reads no checksum, but the pointer table below names the buffers)
+    for (auto& s : sh)
+        if (!s->ring_csum.p) {
+            s->ring_csum.alloc(s->n);
+            RP_HIP(hipMemsetAsync(s->ring_csum.p, 0, s->ring_csum.bytes(), s->st));
+        }
     Shard& s0 = *sh.front();
     if (!route_dir.p) {
         uint32_t bits = 0;
@@ -8098,6 +8119,84 @@ void rp_sim::route_launch(const uint32_t* entries, const uint32_t* keys, uint64_
         stats->requests = stats->local + stats->delivered + stats->checksums_differ + stats->unreachable + stats->entry_dead;
         stats->reserved = 0;
     }
+}
+
+// ---- ownership census -----------------------------------------
+// (after route_prepare(false): the pointer table and the directory exist)
+rp::OwnArgs rp_sim::own_args() {
+    Shard& s0 = *sh.front();
+    rp::OwnArgs A{};
+    A.tab = route_tab.p;
+    A.dead = own_dead.p;
+    A.pt_hash = s0.pt_hash.p; A.pt_server = s0.pt_server.p; A.pt_coll = s0.pt_coll.p;
+    A.dir = route_dir.p;
+    A.srv_pt = own_srv_pt.p;
+    A.n = n; A.nl = s0.nl; A.ncoll = s0.ncoll; A.npts = s0.npts; A.dir_shift = route_dir_shift;
+    A.ntiles = (s0.npts + rp::OWN_TILE - 1) / rp::OWN_TILE;
+    A.diff = own_diff.p; A.claims = own_claims.p; A.tile_sum = own_tile.p;
+    A.claimed = own_claimed.p; A.out = own_out.p;
+    return A;
+}
+
+// The census, unless no call that can change a ring ran since the last one
+// (timed as "other", like a route).  Runs on the first shard's stream.
+void rp_sim::own_refresh() {
+    route_prepare(false);
+    Shard& s0 = *sh.front();
+    const uint32_t npts = s0.npts;
+    if (!own_dead.p) {
+        std::vector<const uint8_t*> h;
+        for (auto& s : sh) h.push_back(s->dead.p);
+        own_dead.alloc(h.size());
+        RP_HIP(hipMemcpy(own_dead.p, h.data(), h.size() * sizeof h[0], hipMemcpyHostToDevice));
+    }
+    if (!own_srv_pt.p) {
+        // every server's replica hashes as the constructor made them, each
+        // row sorted: the device search turns them into point indices
+        std::string blob;
+        std::vector<uint64_t> off{0};
+        for (const std::string& a : s0.addrs) { blob += a; off.push_back(blob.size()); }
+        std::vector<uint32_t> rep;
+        rp::device_replica_hashes(blob, off, rp::REPLICAS, rep, s0.st);
+        if (cfg.replica_hash_shift)
+            for (auto& h : rep) h = (h >> cfg.replica_hash_shift) << cfg.replica_hash_shift;
+        for (size_t sv = 0; sv < n; sv++) std::sort(rep.begin() + sv * rp::REPLICAS, rep.begin() + (sv + 1) * rp::REPLICAS);
+        DevBuf<uint32_t> dh(rep.size()), idx(rep.size());
+        RP_HIP(hipMemcpyAsync(dh.p, rep.data(), rep.size() * 4, hipMemcpyHostToDevice, s0.st));
+        rp::own_point_index(s0.st, own_args(), dh.p, idx.p);
+        RP_HIP(hipGetLastError());
+        RP_HIP(hipStreamSynchronize(s0.st));
+        own_srv_pt = std::move(idx);  // (kept only once it is complete)
+        own_stale = true;
+    }
+    if (!own_stale && own_claims.n == npts && own_claimed.n == n) return;
+    if (own_diff.n != (size_t)npts + 1) own_diff.alloc((size_t)npts + 1);
+    if (own_claims.n != npts) own_claims.alloc(npts);
+    if (own_claimed.n != n) own_claimed.alloc(n);
+    if (!own_out.p) own_out.alloc(rp::OWN_NOUT);
+    const uint32_t ntiles = (npts + rp::OWN_TILE - 1) / rp::OWN_TILE;
+    if (own_tile.n != ntiles) own_tile.alloc(ntiles);
+    const rp::OwnArgs A = own_args();
+    s0.timed(5, [&] {
+        RP_HIP(hipMemsetAsync(own_diff.p, 0, own_diff.bytes(), s0.st));
+        RP_HIP(hipMemsetAsync(own_out.p, 0, own_out.bytes(), s0.st));
+        rp::own_census(s0.st, A);
+    });
+    RP_HIP(hipGetLastError());
+    unsigned long long h[rp::OWN_NOUT];
+    RP_HIP(hipMemcpyAsync(h, own_out.p, sizeof h, hipMemcpyDeviceToHost, s0.st));
+    RP_HIP(hipStreamSynchronize(s0.st));
+    rp_ownership_stats st{};
+    for (int k = 0; k < 8; k++) st.measure[k] = h[rp::OWN_MEASURE + k];
+    st.claimants = h[rp::OWN_CLAIMANTS];
+    st.intervals = npts;
+    st.max_claims = h[rp::OWN_MAX] >> 32;
+    const uint32_t first = ~(uint32_t)h[rp::OWN_MAX];
+    uint32_t hash = 0;
+    if (first < npts) RP_HIP(hipMemcpy(&hash, s0.pt_hash.p + first, 4, hipMemcpyDeviceToHost));
+    st.max_claims_hash = hash;
+    own_stats = st;
+    own_stale = false;
 }
 
 void rp_sim::check_errors() {
@@ -8323,6 +8422,7 @@ int rp_sim_run(rp_sim* s, int k_rounds, int churn_active) {
     return rp::guarded([&] {
         if (!s || k_rounds < 0) throw Error(RP_ERR_INVALID, "bad argument");
         s->ring_csum_stale = true;
+        s->own_stale = true;
         s->run(k_rounds, churn_active != 0);
     });
 }
@@ -8358,6 +8458,7 @@ int rp_sim_node_flags(rp_sim* c, uint32_t node, uint32_t* flags) {
         if (!c || node >= c->n || !flags) throw Error(RP_ERR_INVALID, "bad argument");
         RP_HIP(hipSetDevice(c->dev));
         c->ring_csum_stale = true;
+        c->own_stale = true;
         c->check_errors();
         Shard* s = &c->owner_of(node);
         uint8_t g = 0, q = 0;
@@ -8383,8 +8484,11 @@ int rp_sim_load_addresses(rp_sim* s, const uint8_t* bytes, const uint64_t* off, 
                         "addresses must be loaded before rp_sim_set_views / rp_sim_join / rp_sim_leave / rp_sim_rejoin");
         // (new shards, new points: the routing tables go with the old ones)
         s->ring_csum_stale = true;
+        s->own_stale = true;
         s->route_tab.release();
         s->route_dir.release();
+        s->own_srv_pt.release();
+        s->own_dead.release();
         std::vector<std::string> a(n);
         for (uint32_t i = 0; i < n; i++) {
             if (off[i + 1] < off[i]) throw Error(RP_ERR_INVALID, "offsets must be non-decreasing");
@@ -8422,6 +8526,7 @@ int rp_sim_set_views(rp_sim* s, uint32_t node_lo, uint32_t count, const int32_t*
         if ((uint64_t)node_lo + count > s->n) throw Error(RP_ERR_INVALID, "node range outside the cluster");
         if (!count) return;
         s->ring_csum_stale = true;
+        s->own_stale = true;
         const uint32_t n = s->n;
         std::vector<uint8_t> st((size_t)count * n);
         std::vector<uint64_t> inc((size_t)count * n);
@@ -8469,6 +8574,7 @@ int rp_sim_join(rp_sim* s, const uint32_t* joiners, const uint32_t* rounds, cons
         if (s->round != 0) throw Error(RP_ERR_STATE, "joins can only be scheduled before the first round");
         if (!s->joins.empty()) throw Error(RP_ERR_STATE, "the join schedule is already set");
         s->ring_csum_stale = true;
+        s->own_stale = true;
         const uint32_t n = s->n;
         std::vector<int32_t> jr(n, -1);
         for (uint32_t i = 0; i < count; i++) {
@@ -8573,6 +8679,7 @@ int rp_sim_round(rp_sim* s, int churn_active, rp_round_stats* stats) {
     return rp::guarded([&] {
         if (!s) throw Error(RP_ERR_INVALID, "null sim");
         s->ring_csum_stale = true;
+        s->own_stale = true;
         s->run(1, churn_active != 0);
         s->check_errors();
         if (stats) read_stats(s, s->sh.front()->stats.p, stats, true);
@@ -8764,6 +8871,7 @@ int rp_sim_handle_ping(rp_sim* c, uint32_t node, int64_t source, uint64_t source
     return rp::guarded([&] {
         Shard& s = bridge_shard(c, node);
         c->ring_csum_stale = true;
+        c->own_stale = true;
         if (source < -1 || source >= (int64_t)c->n) throw Error(RP_ERR_INVALID, "bad source");
         // the response (a list or a fullSync) holds at most n changes: check
         // the buffer before the update and the issue change any state
@@ -8799,6 +8907,7 @@ int rp_sim_update(rp_sim* c, uint32_t node, const rp_change* changes, uint32_t n
     return rp::guarded([&] {
         Shard& s = bridge_shard(c, node);
         c->ring_csum_stale = true;
+        c->own_stale = true;
         const uint32_t a = bridge_apply(s, node, changes, n, rp::T0 + rp::PERIOD_MS * c->round);
         bridge_done(c, s);
         if (applied) *applied = a;
@@ -8976,6 +9085,38 @@ int rp_sim_route_uniform(rp_sim* c, uint64_t seed, uint64_t count, rp_route_stat
         c->route_prepare();
         memset(stats, 0, sizeof *stats);
         if (count) c->route_launch<true>(nullptr, nullptr, seed, count, nullptr, nullptr, nullptr, stats);
+    });
+}
+
+int rp_sim_ownership(rp_sim* c, rp_ownership_stats* stats, uint64_t* claimed, size_t cap) {
+    return rp::guarded([&] {
+        if (!c || !stats) throw Error(RP_ERR_INVALID, "null pointer");
+        if (claimed && cap < c->n) throw Error(RP_ERR_INVALID, "claimed buffer holds fewer than n entries");
+        c->own_refresh();
+        static_assert(sizeof(rp_ownership_stats) == 128, "rp_ownership_stats is 16 x u64");
+        *stats = c->own_stats;
+        if (claimed) RP_HIP(hipMemcpy(claimed, c->own_claimed.p, (size_t)c->n * 8, hipMemcpyDeviceToHost));
+    });
+}
+
+int rp_sim_ownership_at(rp_sim* c, const uint32_t* key_hashes, size_t nk, uint32_t* claims) {
+    return rp::guarded([&] {
+        if (!c || (nk && (!key_hashes || !claims))) throw Error(RP_ERR_INVALID, "null pointer");
+        c->own_refresh();
+        if (nk == 0) return;
+        Shard& s0 = *c->sh.front();
+        const rp::OwnArgs A = c->own_args();
+        // (launches of at most 2^30 keys: a thread's index is 32-bit)
+        const size_t chunk = std::min<size_t>(nk, (size_t)1 << 30);
+        DevBuf<uint32_t> dh(chunk), dc(chunk);
+        for (size_t first = 0; first < nk; first += chunk) {
+            const size_t m = std::min(nk - first, chunk);
+            RP_HIP(hipMemcpyAsync(dh.p, key_hashes + first, m * 4, hipMemcpyHostToDevice, s0.st));
+            s0.timed(5, [&] { rp::own_at(s0.st, A, dh.p, (uint32_t)m, dc.p); });
+            RP_HIP(hipGetLastError());
+            RP_HIP(hipMemcpyAsync(claims + first, dc.p, m * 4, hipMemcpyDeviceToHost, s0.st));
+            RP_HIP(hipStreamSynchronize(s0.st));
+        }
     });
 }
 
@@ -9333,6 +9474,7 @@ int rp_traffic_run(rp_traffic* t, int k_rounds, int churn_active, uint64_t per_r
         uint64_t host_bound = t->bound;
         for (int r = 0; r < k_rounds; r++) {
             t->sim->ring_csum_stale = true;
+            t->sim->own_stale = true;
             t->sim->run(1, churn_active != 0);
             t->sim->route_prepare();  // (rp_sim_round's error check; no other readback)
             t->bound = host_bound;

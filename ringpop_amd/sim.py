@@ -3,7 +3,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (RequestPending, RequestResult, RoundStats, RouteStats, SimConfig, TrafficConfig, TrafficStats, check,
+from ._lib import (OwnershipStats, RequestPending, RequestResult, RoundStats, RouteStats, SimConfig, TrafficConfig, TrafficStats, check,
                    lib, ptr)
 
 KERNEL_CATEGORIES = ("churn", "issue", "merge_ping", "merge_resp", "checksum", "other")
@@ -392,6 +392,28 @@ class Sim:
         st = RouteStats()
         check(lib().rp_sim_route_uniform(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(count), ctypes.byref(st)))
         return st.as_dict()
+
+    # ---- ownership census between rounds (rp_sim_ownership)
+    def ownership(self):
+        """How many live nodes claim each key, over the whole 2^32 hash space:
+        a dict of `measure` (hashes with exactly 0..6 claimants, [7]: 7 or
+        more), `claimants`, `intervals`, `max_claims`, `max_claims_hash` and
+        `claimed` (per node the hashes it claims, uint64)."""
+        st = OwnershipStats()
+        claimed = np.zeros(self.n, dtype=np.uint64)
+        check(lib().rp_sim_ownership(self._h, ctypes.byref(st), ptr(claimed), len(claimed)))
+        d = st.as_dict()
+        d["claimed"] = claimed
+        return d
+
+    def ownership_at(self, hashes):
+        """The number of live nodes that claim each key hash (rp_sim_ownership_at)."""
+        h = np.ascontiguousarray(hashes, dtype=np.uint32)
+        if h.ndim != 1:
+            raise ValueError("ownership_at: one array of key hashes")
+        out = np.zeros(len(h), dtype=np.uint32)
+        check(lib().rp_sim_ownership_at(self._h, ptr(h), len(h), ptr(out)))
+        return out
 
     def traffic(self, **cfg):
         """A request tracker on this simulation (rp_traffic_create): max_retries=3,
