@@ -13,7 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libringpop_hip.so")
-SOURCES = ["rp_capi.hip", "rp_ring.hip", "rp_sim.hip", "rp_traffic.hip", "rp_own.hip", "rp_node.hip", "rp_calib.hip"]
+SOURCES = ["rp_capi.hip", "rp_ring.hip", "rp_sim.hip", "rp_route.hip", "rp_traffic.hip", "rp_own.hip", "rp_xport.hip",
+           "rp_node.hip", "rp_calib.hip"]
 _INCLUDE_RE = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)
 
 

@@ -67,6 +67,22 @@ struct WordSink {
     }
 };
 
+// WordSink's emitter into LDS (a wave's rendering buffer), and the wave's
+// fence between writing that buffer and reading it
+struct LdsByteEmit {
+    uint8_t* p;
+    __device__ inline void operator()(uint32_t w) {
+        p[0] = (uint8_t)w; p[1] = (uint8_t)(w >> 8); p[2] = (uint8_t)(w >> 16); p[3] = (uint8_t)(w >> 24);
+        p += 4;
+    }
+};
+// the same for LDS only (s_waitcnt lgkmcnt(0)): loads from global memory
+// issued before it -- the next chunk's prefetch -- stay in flight
+__device__ inline void wave_lds_fence() {
+    __builtin_amdgcn_s_waitcnt(0xC07F);  // vmcnt and expcnt at their maxima, lgkmcnt 0
+    __builtin_amdgcn_wave_barrier();
+}
+
 template <class Sink>
 __device__ __host__ inline void put_dec(Sink& s, uint64_t v) {
     // split into 4-digit groups without arrays (keeps everything in registers)

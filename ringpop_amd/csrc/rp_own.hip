@@ -1,12 +1,42 @@
-// ringpop_amd — the kernels of the ownership census (rp_sim_ownership /
-// rp_sim_ownership_at) and their launches.  None of them is
-// launched by a round.  Every store is a vector store or an integer atomic,
-// and the phases are separate kernels: no block waits for another.
+// ringpop_amd — ownership census (rp_sim_ownership / rp_sim_ownership_at;
+// DESIGN.md §13): for every interval between two ring points, how many live
+// nodes claim it in their own view.  The kernels, the host side that launches
+// them and the two entry points.  None of the kernels is launched by a round.
+// Every store is a vector store or an integer atomic, and the phases are
+// separate kernels: no block waits for another.
 #include <hip/hip_runtime.h>
 
-#include "rp_own.h"
+#include <algorithm>
+
+#include "rp_cluster.h"
 
 namespace rp {
+
+// the census' device results: rp_ownership_stats' measure[8], the claimant
+// count, and the largest claim count packed with its first interval
+// (claims << 32 | ~index, so that an atomic max keeps the lowest index)
+enum : uint32_t { OWN_MEASURE = 0, OWN_CLAIMANTS = 8, OWN_MAX = 9, OWN_NOUT = 10 };
+constexpr uint32_t OWN_REPLICAS = (uint32_t)REPLICAS;
+constexpr uint32_t OWN_BLOCK = 256;     // threads of a scan block ...
+constexpr uint32_t OWN_ITEMS = 8;       // ... and consecutive intervals of each
+constexpr uint32_t OWN_TILE = OWN_BLOCK * OWN_ITEMS;
+constexpr uint32_t OWN_WALK_STEPS = 4;  // backward steps a lane takes alone before the wave searches for it
+
+struct OwnArgs {
+    const RouteShard* tab;            // node v's rows: row v % nl of shard v / nl
+    const uint8_t* const* dead;       // per shard: n bytes by global id (valid for the shard's own nodes)
+    const uint32_t* pt_hash;
+    const int32_t* pt_server;
+    const int32_t* pt_coll;
+    const uint32_t* dir;
+    const uint32_t* srv_pt;           // n x OWN_REPLICAS point indices, each row ascending
+    uint32_t n, nl, ncoll, npts, dir_shift, ntiles;
+    int32_t* diff;                    // npts + 1
+    uint32_t* claims;                 // npts
+    int32_t* tile_sum;                // ntiles: each tile's sum of diff, then its exclusive prefix
+    unsigned long long* claimed;      // n
+    unsigned long long* out;          // OWN_NOUT
+};
 
 // replica hash -> index of its point (every replica hash is a point: the
 // search is exact).  The host sorted each server's hashes, so a row's indices
@@ -210,21 +240,134 @@ static unsigned blocks_for(uint64_t items, unsigned per_block, unsigned cap) {
     return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
 }
 
-void own_point_index(hipStream_t st, const OwnArgs& A, const uint32_t* rep_hash, uint32_t* srv_pt) {
-    hipLaunchKernelGGL(k_own_point_index, dim3(blocks_for((uint64_t)A.n * OWN_REPLICAS, 256, 16384)), dim3(256), 0, st, A,
-                       rep_hash, srv_pt);
-}
-
-// diff and out are zero; A.ntiles = ceil(npts / OWN_TILE)
-void own_census(hipStream_t st, const OwnArgs& A) {
-    hipLaunchKernelGGL(k_own_arcs, dim3((A.n + OWN_BLOCK / 64 - 1) / (OWN_BLOCK / 64)), dim3(OWN_BLOCK), 0, st, A);
-    hipLaunchKernelGGL(k_own_tile_sums, dim3(A.ntiles), dim3(OWN_BLOCK), 0, st, A);
-    hipLaunchKernelGGL(k_own_tile_scan, dim3(1), dim3(64), 0, st, A);
-    hipLaunchKernelGGL(k_own_finish, dim3(A.ntiles), dim3(OWN_BLOCK), 0, st, A);
-}
-
-void own_at(hipStream_t st, const OwnArgs& A, const uint32_t* keys, uint32_t nk, uint32_t* claims_out) {
-    hipLaunchKernelGGL(k_own_at, dim3(blocks_for(nk, 256, 16384)), dim3(256), 0, st, A, keys, nk, claims_out);
-}
-
 }  // namespace rp
+
+// =====================================================================
+// Host side (on the first shard's stream, like a route).
+// =====================================================================
+using rp::DevBuf;
+using rp::Error;
+using rp::Shard;
+
+// (after route_prepare(false): the pointer table and the directory exist)
+rp::OwnArgs rp_sim::own_args() {
+    Shard& s0 = *sh.front();
+    rp::OwnArgs A{};
+    A.tab = route_tab.p;
+    A.dead = own_dead.p;
+    A.pt_hash = s0.pt_hash.p; A.pt_server = s0.pt_server.p; A.pt_coll = s0.pt_coll.p;
+    A.dir = route_dir.p;
+    A.srv_pt = own_srv_pt.p;
+    A.n = n; A.nl = s0.nl; A.ncoll = s0.ncoll; A.npts = s0.npts; A.dir_shift = route_dir_shift;
+    A.ntiles = (s0.npts + rp::OWN_TILE - 1) / rp::OWN_TILE;
+    A.diff = own_diff.p; A.claims = own_claims.p; A.tile_sum = own_tile.p;
+    A.claimed = own_claimed.p; A.out = own_out.p;
+    return A;
+}
+
+// The census, unless no call that can change a ring ran since the last one
+// (timed as "other", like a route).  Runs on the first shard's stream.
+void rp_sim::own_refresh() {
+    route_prepare(false);
+    Shard& s0 = *sh.front();
+    const uint32_t npts = s0.npts;
+    if (!own_dead.p) {
+        std::vector<const uint8_t*> h;
+        for (auto& s : sh) h.push_back(s->dead.p);
+        own_dead.alloc(h.size());
+        RP_HIP(hipMemcpy(own_dead.p, h.data(), h.size() * sizeof h[0], hipMemcpyHostToDevice));
+    }
+    if (!own_srv_pt.p) {
+        // every server's replica hashes as the constructor made them, each
+        // row sorted: the device search turns them into point indices
+        std::string blob;
+        std::vector<uint64_t> off{0};
+        for (const std::string& a : s0.addrs) { blob += a; off.push_back(blob.size()); }
+        std::vector<uint32_t> rep;
+        rp::device_replica_hashes(blob, off, rp::REPLICAS, rep, s0.st);
+        if (cfg.replica_hash_shift)
+            for (auto& h : rep) h = (h >> cfg.replica_hash_shift) << cfg.replica_hash_shift;
+        for (size_t sv = 0; sv < n; sv++) std::sort(rep.begin() + sv * rp::REPLICAS, rep.begin() + (sv + 1) * rp::REPLICAS);
+        DevBuf<uint32_t> dh(rep.size()), idx(rep.size());
+        RP_HIP(hipMemcpyAsync(dh.p, rep.data(), rep.size() * 4, hipMemcpyHostToDevice, s0.st));
+        hipLaunchKernelGGL(rp::k_own_point_index, dim3(rp::blocks_for(rep.size(), 256, 16384)), dim3(256), 0, s0.st,
+                           own_args(), (const uint32_t*)dh.p, idx.p);
+        RP_HIP(hipGetLastError());
+        RP_HIP(hipStreamSynchronize(s0.st));
+        // (kept only once it is complete; the census is stale already: the
+        // index is dropped only where the rings changed, rp_sim_load_addresses)
+        own_srv_pt = std::move(idx);
+    }
+    if (!own_stale && own_claims.n == npts && own_claimed.n == n) return;
+    if (own_diff.n != (size_t)npts + 1) own_diff.alloc((size_t)npts + 1);
+    if (own_claims.n != npts) own_claims.alloc(npts);
+    if (own_claimed.n != n) own_claimed.alloc(n);
+    if (!own_out.p) own_out.alloc(rp::OWN_NOUT);
+    const uint32_t ntiles = (npts + rp::OWN_TILE - 1) / rp::OWN_TILE;
+    if (own_tile.n != ntiles) own_tile.alloc(ntiles);
+    const rp::OwnArgs A = own_args();
+    s0.timed(5, [&] {
+        RP_HIP(hipMemsetAsync(own_diff.p, 0, own_diff.bytes(), s0.st));
+        RP_HIP(hipMemsetAsync(own_out.p, 0, own_out.bytes(), s0.st));
+        // (diff and out are zero; A.ntiles = ceil(npts / OWN_TILE))
+        const unsigned per = rp::OWN_BLOCK / 64;  // views (waves) per block
+        hipLaunchKernelGGL(rp::k_own_arcs, dim3((n + per - 1) / per), dim3(rp::OWN_BLOCK), 0, s0.st, A);
+        hipLaunchKernelGGL(rp::k_own_tile_sums, dim3(ntiles), dim3(rp::OWN_BLOCK), 0, s0.st, A);
+        hipLaunchKernelGGL(rp::k_own_tile_scan, dim3(1), dim3(64), 0, s0.st, A);
+        hipLaunchKernelGGL(rp::k_own_finish, dim3(ntiles), dim3(rp::OWN_BLOCK), 0, s0.st, A);
+    });
+    RP_HIP(hipGetLastError());
+    unsigned long long h[rp::OWN_NOUT];
+    RP_HIP(hipMemcpyAsync(h, own_out.p, sizeof h, hipMemcpyDeviceToHost, s0.st));
+    RP_HIP(hipStreamSynchronize(s0.st));
+    rp_ownership_stats st{};
+    for (int k = 0; k < 8; k++) st.measure[k] = h[rp::OWN_MEASURE + k];
+    st.claimants = h[rp::OWN_CLAIMANTS];
+    st.intervals = npts;
+    st.max_claims = h[rp::OWN_MAX] >> 32;
+    const uint32_t first = ~(uint32_t)h[rp::OWN_MAX];
+    uint32_t hash = 0;
+    if (first < npts) RP_HIP(hipMemcpy(&hash, s0.pt_hash.p + first, 4, hipMemcpyDeviceToHost));
+    st.max_claims_hash = hash;
+    own_stats = st;
+    own_stale = false;
+}
+
+extern "C" {
+
+int rp_sim_ownership(rp_sim* c, rp_ownership_stats* stats, uint64_t* claimed, size_t cap) {
+    return rp::guarded([&] {
+        if (!c || !stats) throw Error(RP_ERR_INVALID, "null pointer");
+        if (claimed && cap < c->n) throw Error(RP_ERR_INVALID, "claimed buffer holds fewer than n entries");
+        c->own_refresh();
+        static_assert(sizeof(rp_ownership_stats) == 128, "rp_ownership_stats is 16 x u64");
+        *stats = c->own_stats;
+        if (claimed) RP_HIP(hipMemcpy(claimed, c->own_claimed.p, (size_t)c->n * 8, hipMemcpyDeviceToHost));
+    });
+}
+
+int rp_sim_ownership_at(rp_sim* c, const uint32_t* key_hashes, size_t nk, uint32_t* claims) {
+    return rp::guarded([&] {
+        if (!c || (nk && (!key_hashes || !claims))) throw Error(RP_ERR_INVALID, "null pointer");
+        c->own_refresh();
+        if (nk == 0) return;
+        Shard& s0 = *c->sh.front();
+        const rp::OwnArgs A = c->own_args();
+        // (launches of at most 2^30 keys: a thread's index is 32-bit)
+        const size_t chunk = std::min<size_t>(nk, (size_t)1 << 30);
+        DevBuf<uint32_t> dh(chunk), dc(chunk);
+        for (size_t first = 0; first < nk; first += chunk) {
+            const size_t m = std::min(nk - first, chunk);
+            RP_HIP(hipMemcpyAsync(dh.p, key_hashes + first, m * 4, hipMemcpyHostToDevice, s0.st));
+            s0.timed(5, [&] {
+                hipLaunchKernelGGL(rp::k_own_at, dim3(rp::blocks_for(m, 256, 16384)), dim3(256), 0, s0.st, A,
+                                   (const uint32_t*)dh.p, (uint32_t)m, dc.p);
+            });
+            RP_HIP(hipGetLastError());
+            RP_HIP(hipMemcpyAsync(claims + first, dc.p, m * 4, hipMemcpyDeviceToHost, s0.st));
+            RP_HIP(hipStreamSynchronize(s0.st));
+        }
+    });
+}
+
+}  // extern "C"

@@ -1,7 +1,12 @@
-// Device-resident simulation of N ringpop instances (host-side declarations).
+// Device-resident simulation of N ringpop instances: the device state
+// (SimDev) and the plain records of its buffers, shared by the round kernels
+// (rp_sim.hip), the between-round kernels (rp_route.hip, rp_traffic.hip,
+// rp_own.hip) and the host types that allocate them (rp_cluster.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <cstddef>
 
 #include <string>
 #include <vector>
@@ -284,5 +289,79 @@ __host__ __device__ inline uint8_t* suspicion_off(const SimDev& S) { return S.de
 __device__ inline bool unreachable(const SimDev& S, uint32_t from, uint32_t to) {
     return S.dead[to] || cut(S, from, to);
 }
+
+// ---- plain records of the round kernels' buffers.  The host allocates
+// them (Shard, rp_cluster.h) and the kernels of rp_sim.hip fill and read them.
+
+// a checksum-cache entry: {view fingerprint, check word | checksum} (rp_sim.hip: ck_pack)
+struct CkEntry { unsigned long long key, val; };
+// k_p2_pre: one ping rank's respond record
+struct alignas(16) P2Rec {  // (k_p2_respond reads it as 8 words: keep the layout)
+    uint32_t b, Ad;
+    uint64_t sv;
+    uint64_t req_inc, req_fp;
+};
+static_assert(sizeof(P2Rec) == 32 && offsetof(P2Rec, sv) == 8 && offsetof(P2Rec, req_fp) == 24,
+              "k_p2_pre record: 32 bytes, read as words by k_p2_respond");
+// one segment copy of an in-process exchange, and a launch's worth of them (k_copy_batch)
+struct CopyDesc {
+    const void* src;
+    void* dst;
+    uint64_t bytes;
+};
+constexpr uint32_t COPY_BATCH = 128;  // (the batch travels as a 3 KB kernel argument)
+struct CopyBatch {
+    uint32_t n, pad;
+    CopyDesc d[COPY_BATCH];
+};
+// one buffer reset of a round, and a launch's worth of them (k_fill_batch, k_round_start)
+struct FillDesc {
+    void* dst;
+    uint64_t bytes;  // a multiple of 4
+    uint32_t word;   // the byte value repeated
+    uint32_t pad;
+};
+constexpr uint32_t FILL_BATCH = 16;
+struct FillBatch {
+    uint32_t n, pad;
+    FillDesc d[FILL_BATCH];
+};
+// a sender's ping metadata, all-gathered by sharded rounds (k_meta_pack)
+struct PingMeta {
+    int32_t target;
+    uint32_t len, plen, min_cnt;
+    int32_t ring_count;
+    uint32_t nesc;
+    uint64_t inc, fp;
+    uint64_t min_l1, min_l2;
+    uint32_t min_safe;
+    int32_t max_pb;
+};
+static_assert(sizeof(PingMeta) == 64, "ping metadata is 64 bytes");
+struct RespRec {  // a response crossing shards: kind, reference list length, words and escapes shipped
+    int32_t kind;
+    uint32_t len, psize, pesc;
+};
+constexpr uint32_t MAXG = 64;  // shards per cluster
+// a ping-req wave's message crossing shards (k_xs_*)
+struct SlotRec {
+    uint32_t slot;
+    int32_t dest;
+    int32_t kind;         // W3: 0; W4: 1 = PingReqPingError back to A; W5/W6: Resp kind
+    uint32_t len;         // the reference's list length
+    uint32_t plen, nesc;  // entries shipped, and of those escapes
+    uint32_t aux;         // W4: the relay K; W5/W6: the responder
+    uint32_t csum;        // W3: A's checksum (its ping-req body); W4: K's
+    uint32_t ping_status;
+    uint32_t woff, eoff;  // payload offsets inside the partner segment
+    uint32_t pad;
+    uint64_t inc, fp;     // W3: A's incarnation / fingerprint; W4: K's
+};
+static_assert(sizeof(SlotRec) == 64, "slot record is 64 bytes");
+
+constexpr uint32_t SEEN_STAGE_WORDS = 1024;  // seen windows up to 32,768 ids are staged in LDS
+#ifndef RP_ISSUE_WAVE
+#define RP_ISSUE_WAVE 1  // the default of rp_sim_config.issue_wave: 1 = wave kernels where eligible, 0 = block kernels
+#endif
 
 }  // namespace rp

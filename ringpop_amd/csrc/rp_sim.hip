@@ -28,9 +28,7 @@
 
 #include <algorithm>
 #include <chrono>
-#include <condition_variable>
 #include <memory>
-#include <mutex>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -211,7 +209,6 @@ struct Shared {
 // struct up to the end of `ring` (its other users -- wg_compact's gbase -- lie inside)
 constexpr size_t APPLY_LDS_BYTES_ = offsetof(Shared, ring) + sizeof(uint32_t) * 1024;
 static_assert(offsetof(Shared, gbase) + sizeof(uint32_t) * 512 <= APPLY_LDS_BYTES_, "wg_compact scratch inside the merge LDS");
-constexpr uint32_t SEEN_STAGE_WORDS = 1024;  // seen windows up to 32,768 ids are staged in LDS
 static_assert(SEEN_STAGE_WORDS == 4 * BLOCK, "stage_seen: one 16-byte load per thread");
 // Stage a seen bitset (seen_words words) in LDS: one 16-byte load per thread
 // when rows are 16-byte multiples (windows >= 128 ids), so the copy costs one
@@ -1766,9 +1763,6 @@ __device__ uint32_t wg_issue(const SimDev& S, uint32_t v, bool filter, uint32_t 
 // itself -- no masks, scans, stash per wave or reductions through LDS, and no
 // workgroup barrier anywhere.  Log positions after the issue (expiries, prefix
 // packing, compaction) are wg_issue's for the same inputs.
-#ifndef RP_ISSUE_WAVE
-#define RP_ISSUE_WAVE 1  // the default of rp_sim_config.issue_wave: 1 = wave kernels where eligible, 0 = block kernels
-#endif
 #ifndef RP_WAVE_UNR
 #define RP_WAVE_UNR 8  // wave_issue: groups in flight
 #endif
@@ -2830,21 +2824,8 @@ __global__ void k_need_checksums(SimDev S, const uint32_t* fd, uint32_t nfd, uin
 constexpr uint32_t CKW_TEXT = 3712;  // < 20 carried + 64 x (1 + 32 + 7 + 16) rendered bytes
 constexpr uint32_t CKW_PRE = 184;    // >= the 20-byte blocks of one chunk (CKW_TEXT / 20)
 constexpr uint32_t CKW_BUF = CKW_TEXT + CKW_PRE * 48;  // + their fh_stream_pre records
-struct LdsByteEmit {
-    uint8_t* p;
-    __device__ inline void operator()(uint32_t w) {
-        p[0] = (uint8_t)w; p[1] = (uint8_t)(w >> 8); p[2] = (uint8_t)(w >> 16); p[3] = (uint8_t)(w >> 24);
-        p += 4;
-    }
-};
 __device__ inline void wave_lds_sync() {
     __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_wave_barrier();
-}
-// the same for LDS only (s_waitcnt lgkmcnt(0)): loads from global memory
-// issued before it -- the next chunk's prefetch -- stay in flight
-__device__ inline void wave_lds_fence() {
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // vmcnt and expcnt at their maxima, lgkmcnt 0
     __builtin_amdgcn_wave_barrier();
 }
 template <class RowFn>
@@ -3501,7 +3482,6 @@ constexpr unsigned long long FP_EMPTY = ~0ull;
 // assumption as the per-call dedupe): a direct-mapped cache of {fingerprint,
 // check word | checksum}.  Entries are written without locks; the check word
 // (a mix of both halves) rejects an entry torn between two writers.
-struct CkEntry { unsigned long long key, val; };
 __device__ inline uint32_t ck_slot(unsigned long long f, uint32_t mask) {
     return (uint32_t)((f * 0x9E3779B97F4A7C15ull) >> 32) & mask;
 }
@@ -3836,13 +3816,6 @@ k_p2_apply(SimDev S, uint64_t now, uint32_t k, const uint32_t* list, const uint3
 // (the requester's need_csum rides in Ad: P2_NEED; a ping's pending fullSync
 // decision compares with snd_csum[A] in k_pending, PEND_SND)
 constexpr uint32_t P2_NEED = 0x40000000u;
-struct alignas(16) P2Rec {  // (k_p2_respond reads it as 8 words: keep the layout)
-    uint32_t b, Ad;
-    uint64_t sv;
-    uint64_t req_inc, req_fp;
-};
-static_assert(sizeof(P2Rec) == 32 && offsetof(P2Rec, sv) == 8 && offsetof(P2Rec, req_fp) == 24,
-              "k_p2_pre record: 32 bytes, read as words by k_p2_respond");
 __global__ void __launch_bounds__(256) k_p2_pre(SimDev S, const uint32_t* list, const uint32_t* len, P2Rec* rec) {
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t cnt = *len;
@@ -4828,16 +4801,6 @@ __global__ void k_self_inc(SimDev S) {
 // (blockIdx.y = segment) instead of a copy launch per (source, destination)
 // pair -- G (G - 1) of them per all-to-all or all-gather, a few hundred per
 // sharded round, each costing a launch on the cluster stream.
-struct CopyDesc {
-    const void* src;
-    void* dst;
-    uint64_t bytes;
-};
-constexpr uint32_t COPY_BATCH = 128;  // (the batch travels as a 3 KB kernel argument)
-struct CopyBatch {
-    uint32_t n, pad;
-    CopyDesc d[COPY_BATCH];
-};
 __global__ void __launch_bounds__(256) k_copy_batch(CopyBatch b) {
     const CopyDesc c = b.d[blockIdx.y];
     const uint64_t stride = (uint64_t)gridDim.x * 256, t0 = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -4860,17 +4823,6 @@ __global__ void __launch_bounds__(256) k_copy_batch(CopyBatch b) {
 // The round's buffer resets in one launch (blockIdx.y = buffer) instead of a
 // fill launch per buffer: a sharded round is a chain of short launches per
 // shard, and each memset was one more.
-struct FillDesc {
-    void* dst;
-    uint64_t bytes;  // a multiple of 4
-    uint32_t word;   // the byte value repeated
-    uint32_t pad;
-};
-constexpr uint32_t FILL_BATCH = 16;
-struct FillBatch {
-    uint32_t n, pad;
-    FillDesc d[FILL_BATCH];
-};
 __device__ inline void fill_desc(const FillDesc& f, uint32_t x, uint32_t gx) {
     uint32_t* d = (uint32_t*)f.dst;
     for (uint64_t i = (uint64_t)x * 256 + threadIdx.x; i < f.bytes / 4; i += (uint64_t)gx * 256) d[i] = f.word;
@@ -5102,21 +5054,6 @@ __global__ void k_bridge_checksum(SimDev S, uint32_t v, uint64_t* out) {
 // in ascending sender id, so both sides derive the same offsets from the
 // replicated metadata and no count exchange is needed for pings.
 // =====================================================================
-struct PingMeta {
-    int32_t target;
-    uint32_t len, plen, min_cnt;
-    int32_t ring_count;
-    uint32_t nesc;
-    uint64_t inc, fp;
-    uint64_t min_l1, min_l2;
-    uint32_t min_safe;
-    int32_t max_pb;
-};
-static_assert(sizeof(PingMeta) == 64, "ping metadata is 64 bytes");
-struct RespRec {  // a response crossing shards: kind, reference list length, words and escapes shipped
-    int32_t kind;
-    uint32_t len, psize, pesc;
-};
 // Exchange counts per partner shard (XC_NCAT x G, entries of the segment):
 // ping words / escapes, response records, response words / escapes.
 enum {
@@ -5153,7 +5090,6 @@ __global__ void k_meta_unpack(SimDev S, const PingMeta* meta) {
 // with three counters at once; offsets come out relative to the segment and
 // k_plan_fix adds the segment bases once every partner's total is known.
 constexpr int XB = 1024;
-constexpr uint32_t MAXG = 64;  // shards per cluster
 struct U3 { uint64_t a, b, c; };
 
 // Exclusive tile-wise scan of get(i) (three counters; zero for non-members)
@@ -5418,20 +5354,6 @@ __global__ void __launch_bounds__(BLOCK) k_expand_pings(SimDev S) {
 // W5; W6 responses are merged from rx2w).  Unlike pings, the receiver cannot
 // derive which slots will arrive, so the per-partner counts are all-gathered
 // first.
-struct SlotRec {
-    uint32_t slot;
-    int32_t dest;
-    int32_t kind;         // W3: 0; W4: 1 = PingReqPingError back to A; W5/W6: Resp kind
-    uint32_t len;         // the reference's list length
-    uint32_t plen, nesc;  // entries shipped, and of those escapes
-    uint32_t aux;         // W4: the relay K; W5/W6: the responder
-    uint32_t csum;        // W3: A's checksum (its ping-req body); W4: K's
-    uint32_t ping_status;
-    uint32_t woff, eoff;  // payload offsets inside the partner segment
-    uint32_t pad;
-    uint64_t inc, fp;     // W3: A's incarnation / fingerprint; W4: K's
-};
-static_assert(sizeof(SlotRec) == 64, "slot record is 64 bytes");
 
 // Does slot s carry a wave-W message from this shard to another?  Its
 // destination, and the words / escapes of its list.
@@ -5675,273 +5597,16 @@ __global__ void k_stats_combine(SimDev S, const unsigned long long* g, unsigned 
     totals[STAT_NSTATS] += conv ? 1ull : 0ull;
 }
 
-// ------------------------------------------------------------ request routing
-// Between rounds (rp_sim_ring_checksums / rp_sim_route / rp_sim_route_uniform;
-// DESIGN.md §10): the ring checksum of every view and, for batches of
-// requests, the outcome handleOrProxy and the request proxy would see.  None
-// of these kernels is launched by a round.
-
-// HashRing.checksum of one view by a whole wave (lib/ring.js:96-105): the
-// structure of wave_view_checksum for the string of the in-ring members'
-// addresses joined by ';'.  Pass 1 takes the length, the member count and the
-// last member; the last 20 bytes come from rendering the top chunks that cover
-// them; then the chunks are rendered in order into the wave's LDS buffer at
-// prefix-sum offsets and their whole 20-byte blocks hashed (FhLanes), the
-// leftover bytes carried to the buffer's front.  A string of <= 24 bytes is
-// rendered whole and hashed by farmhash32's short branches.
-constexpr uint32_t RCK_TEXT = 2240;  // > 20 carried + 64 x (1 + 32) rendered bytes; a multiple of 16
-constexpr uint32_t RCK_PRE = RCK_TEXT / 20;  // >= the 20-byte blocks of one chunk
-constexpr uint32_t RCK_BUF = RCK_TEXT + RCK_PRE * 48;  // + their fh_stream_pre records
-static_assert(RCK_TEXT % 16 == 0 && RCK_BUF % 16 == 0, "the records are read as 16-byte words");
-static_assert(RCK_TEXT >= 20 + 64 * (1 + 4 * ADDR_WORDS), "a chunk and the carried bytes fit");
-
-// One chunk of 64 members: every lane whose member is in the ring writes
-// [';'] + its address at buf + base + (the lanes' prefix sum); returns the
-// chunk's bytes.
-__device__ inline uint32_t ring_render_chunk(uint8_t* buf, uint32_t base, bool present, bool sep, uint32_t L,
-                                             const uint4& wa, const uint4& wb) {
-    const uint32_t lane = lane_id();
-    const uint32_t b = present ? L + (sep ? 1u : 0u) : 0u;
-    uint32_t incl = b;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(incl, o);
-        if ((int)lane >= o) incl += y;
-    }
-    const uint32_t total = __shfl(incl, 63);
-    if (present) {
-        WordSink<LdsByteEmit> w;
-        w.emit.p = buf + base + (incl - b);
-        if (sep) w.put(0x3Bu, 1);
-        const uint32_t aw[ADDR_WORDS] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
-#pragma unroll
-        for (uint32_t k = 0; k < ADDR_WORDS; k++)
-            if (k * 4 < L) w.put(aw[k], L - 4 * k >= 4 ? 4 : L - 4 * k);
-        for (uint32_t i = 0; i < w.bits / 8; i++) w.emit.p[i] = (uint8_t)(w.acc >> (8 * i));
-    }
-    return total;
-}
-
-__device__ uint32_t wave_ring_checksum(const uint8_t* row, uint32_t n, const AddrTable& at, uint8_t* buf) {
-    const uint32_t lane = lane_id();
-    // pass 1 (parallel): string length, server count, last server
-    uint64_t len = 0, cnt = 0;
-    uint32_t lastp1 = 0;
-#pragma unroll 4
-    for (uint32_t a = lane; a < n; a += 64) {
-        const uint32_t in = row[a], L = at.len[a];
-        len += in ? L : 0u;
-        cnt += in ? 1u : 0u;
-        lastp1 = in ? a + 1 : lastp1;
-    }
-    len = wave_sum64(len);
-    cnt = wave_sum64(cnt);
-    if (cnt == 0) return farmhash32(nullptr, 0);
-    len += cnt - 1;
-    const uint32_t last = ~wave_min32(~lastp1) - 1;
-    const bool small = len <= 24;
-    auto load = [&](uint32_t a, bool& present, uint32_t& L, uint4& wa, uint4& wb) {
-        present = a < n && row[a] != 0;
-        L = 0;
-        wa = make_uint4(0, 0, 0, 0);
-        wb = wa;
-        if (a < n) {
-            L = at.len[a];
-            const uint4* p = (const uint4*)(at.words + (size_t)a * ADDR_WORDS);
-            wa = p[0];
-            wb = p[1];
-        }
-    };
-    FhStream st;
-    st.blocks_left = 0;
-    if (!small) {
-        // the last 20 bytes: chunks from the top down until they cover them
-        // (every member with a ';' before it; only a ring's first member has
-        // none, and that byte lies more than 20 bytes before the end)
-        uint32_t T = 0, c_lo = last & ~63u;
-        for (uint32_t c = c_lo;; c -= 64) {
-            const uint32_t a = c + lane;
-            const bool present = a < n && row[a] != 0;
-            T += (uint32_t)wave_sum64(present ? at.len[a] + 1u : 0u);
-            c_lo = c;
-            if (T >= 20 || c == 0) break;
-        }
-        // (chunks above c_lo hold < 20 bytes, c_lo's at most 64 x 33: T < RCK_TEXT)
-        uint32_t off = 0;
-        for (uint32_t c = c_lo; c <= last; c += 64) {
-            bool present;
-            uint32_t L;
-            uint4 wa, wb;
-            load(c + lane, present, L, wa, wb);
-            if (__ballot(present) == 0) continue;
-            off += ring_render_chunk(buf, off, present, present, L, wa, wb);
-        }
-        wave_lds_fence();
-        const uint8_t* t = buf + off - 20;
-        st = fh_stream_begin5((uint32_t)len, fetch32(t), fetch32(t + 4), fetch32(t + 8), fetch32(t + 12), fetch32(t + 16));
-        wave_lds_fence();
-    }
-    FhLanes fl;
-    fl.init(st);
-    uint32_t carry = 0;
-    bool any_before = false;
-    // the next chunk's ring bytes and addresses are in flight while this one
-    // renders and hashes
-    bool p_n;
-    uint32_t L_n;
-    uint4 wa_n, wb_n;
-    load(lane, p_n, L_n, wa_n, wb_n);
-    for (uint32_t c0 = 0; c0 <= last && (small || st.blocks_left); c0 += 64) {
-        const bool present = p_n;
-        const uint32_t L = L_n;
-        const uint4 aw0 = wa_n, aw1 = wb_n;
-        load(c0 + 64 + lane, p_n, L_n, wa_n, wb_n);
-        const uint64_t m = __ballot(present);
-        if (m == 0) continue;
-        const bool sep = present && (any_before || (m & ((1ull << lane) - 1ull)) != 0);
-        const uint32_t total = ring_render_chunk(buf, carry, present, sep, L, aw0, aw1);
-        any_before = true;
-        wave_lds_fence();
-        const uint32_t avail = carry + total;
-        const uint32_t nb = small ? 0u : min(avail / 20u, st.blocks_left);
-        const uint32_t* wb = (const uint32_t*)buf;
-        uint32_t* const pre = (uint32_t*)(buf + RCK_TEXT);
-        for (uint32_t j = lane; j < nb; j += 64)
-            fh_stream_pre_sliced(wb[5 * j], wb[5 * j + 1], wb[5 * j + 2], wb[5 * j + 3], wb[5 * j + 4], pre + 12 * j);
-        wave_lds_fence();
-        fl.run((const uint4*)pre, 0, nb);
-        st.blocks_left -= nb;
-        const uint32_t left = avail - 20u * nb;
-        // (while blocks remain, left < 20 <= 20 nb or nb = 0: no overlapping move)
-        uint8_t mv = 0;
-        if (nb && st.blocks_left && lane < left) mv = buf[20u * nb + lane];
-        wave_lds_fence();
-        if (nb && st.blocks_left && lane < left) buf[lane] = mv;
-        wave_lds_fence();
-        carry = left;
-    }
-    if (small) return farmhash32(buf, (uint32_t)len);
-    return fh_stream_end(fl.get(0));
-}
-
-// Ring checksums of this shard's views, one wave per view (grid-stride).
-__global__ void __launch_bounds__(BLOCK) k_ring_checksums(SimDev S, uint32_t* out) {
-    __shared__ __attribute__((aligned(16))) uint8_t bufs[NWAVE][RCK_BUF];
-    const AddrTable at{S.addr_words, S.addr_len};
-    for (uint32_t i = blockIdx.x * NWAVE + wave_id(); i < S.nl; i += gridDim.x * NWAVE) {
-        const uint32_t v = S.lo + i;
-        const uint32_t c = wave_ring_checksum(S.in_ring + S.row(v), S.n, at, bufs[wave_id()]);
-        if (lane_id() == 0) out[v] = c;
-    }
-}
-
-// Bucket directory over the sorted point hashes: dir[b] = lower bound of
-// b << shift for b in [0, nb], dir[nb] = npts.  The points are fixed once the
-// addresses are, so it is built once.
-__global__ void k_route_dir(const uint32_t* pt_hash, uint32_t npts, uint32_t shift, uint32_t nb, uint32_t* dir) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b > nb) return;
-    uint32_t lo = 0, hi = npts;
-    if (b == nb) lo = npts;
-    const uint32_t key = (uint32_t)((uint64_t)b << shift);
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (pt_hash[m] < key) lo = m + 1; else hi = m; }
-    dir[b] = lo;
-}
-
-enum : uint32_t { ROUTE_LOCAL = 0, ROUTE_DELIVERED = 1, ROUTE_CHECKSUMS_DIFFER = 2, ROUTE_UNREACHABLE = 3,
-                  ROUTE_ENTRY_DEAD = 4, ROUTE_MISROUTED = 5, ROUTE_NCOUNT = 6 };
-
-// Requests [0, count): request i is (entries[i], keys[i]) or, UNIFORM, drawn
-// from splitmix64 at index first + i.  One thread per request (grid-stride):
-// one binary search inside the key's directory bucket, then the walk in the
-// entry's view and, for a proxied request, in the destination's from the same
-// point.  S carries the clock (round, partition window) and the liveness
-// bytes; counts are kept per thread, summed per block in LDS and flushed with
-// one atomic per counter and block.
-template <bool UNIFORM>
-__global__ void __launch_bounds__(256) k_route(SimDev S, const RouteShard* tab, const uint32_t* pt_hash,
-                                               const int32_t* pt_server, const int32_t* pt_coll, uint32_t npts,
-                                               const uint32_t* dir, uint32_t dir_shift, const uint32_t* entries,
-                                               const uint32_t* keys, uint64_t seed, uint64_t first, uint64_t count,
-                                               int32_t* dests, uint8_t* outcomes, uint8_t* agrees,
-                                               unsigned long long* stats) {
-    __shared__ unsigned long long bc[ROUTE_NCOUNT];
-    if (threadIdx.x < ROUTE_NCOUNT) bc[threadIdx.x] = 0;
-    __syncthreads();
-    uint32_t c[ROUTE_NCOUNT] = {0, 0, 0, 0, 0, 0};
-    auto ring_of = [&](uint32_t v, const RouteShard& t) { return route_ring_of(S, t, v); };
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (uint64_t)gridDim.x * 256) {
-        uint32_t e, h;
-        if (UNIFORM) {
-            // request first + i: splitmix64's finaliser of seed + (first + i + 1) x the golden gamma
-            uint64_t s = seed + (first + i) * 0x9E3779B97F4A7C15ULL;
-            const uint64_t r = splitmix_next(s);
-            e = (uint32_t)(((r >> 32) * S.n) >> 32);
-            h = (uint32_t)r;
-        } else {
-            e = entries[i];
-            h = keys[i];
-        }
-        int32_t dest = -1;
-        uint32_t oc = ROUTE_ENTRY_DEAD, ag = 0;
-        if (!S.dead[e]) {
-            const RouteShard& te = tab[e / S.nl];
-            int32_t d = -1;
-            uint32_t p = 0;
-            if (te.ring_count[e] > 0) {
-                p = route_point(pt_hash, npts, dir, dir_shift, h);
-                d = route_walk(ring_of(e, te), pt_server, pt_coll, npts, p);
-            }
-            if (d < 0 || (uint32_t)d == e) {
-                oc = ROUTE_LOCAL;
-                dest = (int32_t)e;
-            } else {
-                dest = d;
-                if (unreachable(S, e, (uint32_t)d)) {
-                    oc = ROUTE_UNREACHABLE;
-                } else {
-                    const RouteShard& td = tab[(uint32_t)d / S.nl];
-                    oc = te.ring_csum[e] != td.ring_csum[d] ? ROUTE_CHECKSUMS_DIFFER : ROUTE_DELIVERED;
-                    const int32_t d2 =
-                        td.ring_count[d] > 0 ? route_walk(ring_of((uint32_t)d, td), pt_server, pt_coll, npts, p) : -1;
-                    ag = d2 == d ? 1u : 0u;
-                    if (!ag) c[ROUTE_MISROUTED]++;
-                }
-            }
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < ROUTE_MISROUTED; k++) c[k] += oc == k ? 1u : 0u;  // (registers: no indexed access)
-        if (dests) dests[i] = dest;
-        if (outcomes) outcomes[i] = (uint8_t)oc;
-        if (agrees) agrees[i] = (uint8_t)ag;
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < ROUTE_NCOUNT; k++)
-        if (c[k]) atomicAdd(&bc[k], (unsigned long long)c[k]);
-    __syncthreads();
-    if (threadIdx.x < ROUTE_NCOUNT && bc[threadIdx.x]) atomicAdd(&stats[threadIdx.x], bc[threadIdx.x]);
-}
-
 }  // namespace rp
 
 // =====================================================================
 // Host side: rp_sim objects and their C ABI.
 // =====================================================================
-#include <rccl/rccl.h>
-
-#include <map>
-#include <memory>
-
+#include "rp_cluster.h"
 #include "rp_internal.h"
-#include "rp_own.h"
 
-namespace {
+namespace rp {
 
-using rp::Change;
-using rp::DevBuf;
-using rp::Error;
-
-constexpr int NCAT = 7;  // churn, issue, merge_ping, merge_resp, checksum, other, exchange
 #ifndef RP_CK_SIDE
 #define RP_CK_SIDE 1  // one shard: the round's sender checksums and fullSync decisions on a side stream
 #endif
@@ -5949,252 +5614,43 @@ constexpr int NCAT = 7;  // churn, issue, merge_ping, merge_resp, checksum, othe
 #define RP_CK_SIDE_MB 4096  // the side stream's leader view copies (config 5 at 65,536: 8,192 rows of 512 KB,
                            // enough for the mass failure's first rounds)
 #endif
-constexpr uint32_t CHURN_SLOTS = 1024;  // rounds of churn ids staged per copy
 
-struct TimedSpan {
-    int cat;
-    hipEvent_t a, b;
-};
+// seen_clear: the last batch also clears the round's seen bits (k_round_start)
+void Shard::fill_flush(bool seen_clear) {
+    for (size_t i0 = 0; i0 < fills.size() || (seen_clear && i0 == 0); i0 += rp::FILL_BATCH) {
+        rp::FillBatch b{};
+        b.n = (uint32_t)std::min<size_t>(rp::FILL_BATCH, fills.size() - i0);
+        uint64_t mx = 0;
+        for (uint32_t j = 0; j < b.n; j++) { b.d[j] = fills[i0 + j]; mx = std::max<uint64_t>(mx, b.d[j].bytes); }
+        const uint32_t gx = (uint32_t)std::min<uint64_t>(256, std::max<uint64_t>(1, (mx / 4 + 255) / 256));
+        if (seen_clear && i0 + rp::FILL_BATCH >= fills.size())
+            hipLaunchKernelGGL(rp::k_round_start, dim3(gx * b.n + (nl + 3) / 4), dim3(256), 0, st, b, gx, d);
+        else
+            hipLaunchKernelGGL(rp::k_fill_batch, dim3(gx, b.n), dim3(256), 0, st, b);
+    }
+    fills.clear();
+}
 
+// the pending fullSync decisions (k_pending)
+void Shard::launch_pending(hipStream_t s) {
+    hipLaunchKernelGGL(rp::k_pending, dim3(std::min(rp::grid_for(d.snap_cap, rp::NWAVE), 8192u)), dim3(rp::BLOCK), 0,
+                       s, d);
+}
 
-struct Shard {
-    rp_sim_config cfg{};
-    uint32_t n = 0, k = 0;
-    uint32_t lo = 0, nl = 0, rank = 0, G = 1;  // this shard holds nodes [lo, lo + nl) of G shards
-    bool one_per_process = false;  // exchanges over RCCL (rp_sim_create_rank)
-    hipStream_t st = nullptr;
-    bool own_stream = false;
-    hipEvent_t xev = nullptr;  // in-process clusters: this shard's stream reached an exchange step
-    rp::SimDev d{};
-    DevBuf<rp::VEnt> view;
-    DevBuf<uint64_t> fp, rng, snd_inc, snd_fp, msg_off, snaps, pr_inc, pr_fp, pq_off, rl_off, rl_inc, rl_fp;
-    DevBuf<uint32_t> mcount, snap_ord, snap_m;
-    DevBuf<uint32_t> order, dhead, dtail, csum, csum_valid, addr_words, msg_len, msg_plen, snd_csum, g_cnt, g_fill, g_base,
-        g_list, snap_count, pend_slot, pend_csum, origin_count, err, conv, pr_n, pr_errors, pr_bad, pr_done, pr_csum,
-        pq_len, rl_len, rl_csum, thead, ttail;
-    DevBuf<Change> arena;
-    DevBuf<uint32_t> dko;
-    DevBuf<uint32_t> dad;
-    DevBuf<uint32_t> p2_list, p2_len;  // k_p2_lists: receivers per ping rank
-    DevBuf<uint64_t> p2_msg;           // ... and their pings' bodies (k_p2_apply)
-    DevBuf<rp::P2Rec> p2_rec;          // k_p2_pre: one rank's respond records (k_p2_respond)
-    DevBuf<uint64_t> dvs;
-    DevBuf<rp::Resp> resp;
-    DevBuf<uint2> tfifo;
-    DevBuf<int32_t> storm;  // CHURN_SLOTS x 2 x storm_kmax: per round, accusers then victims (k_storm)
-    uint32_t storm_kmax = 0;
-    DevBuf<int32_t> max_pb, ring_count, coll_owner, coll_of, iter_index, iter_round, npingable, target, churn_ids,
-        pt_server, pt_coll, w3_dest, w4_dest, w5_dest, w6_dest, dead_ids;
-    DevBuf<uint64_t> sv_word;  // k_phase1: same-view decisions
-    DevBuf<uint8_t> in_ring, dead, addr_len, need_shuffle, need_csum, pend_done, w4_err;
-    DevBuf<uint32_t> shuf_list, shuf_count, g_tile, g_bloc;  // k_iterate: nodes whose iterator wrapped this round
-    DevBuf<uint64_t> min_l1, min_l2;
-    DevBuf<uint32_t> min_safe, min_cnt, dangerous, dlive, icount, seen, oc_snap, coll_off, coll_ids, rbatch, self_origin;
-    DevBuf<uint32_t> cmem_off, cmem;  // per collision group, its servers (ascending): rp_sim_set_views' ring owners
-    DevBuf<uint64_t> self_inc;
-    DevBuf<int64_t> slen;
-    DevBuf<uint32_t> ck_list, ck_count;  // views queued for k_checksums
-    DevBuf<uint32_t> ring_csum;          // n: this shard's nodes' ring checksums (rp_sim_ring_checksums; on first use)
-    DevBuf<unsigned long long> hkey;      // Shard::checksums: fingerprint table
-    DevBuf<uint32_t> hval, ck_lead, ck_nlead, ck_slot;
-    DevBuf<rp::CkEntry> ck_cache;
-    // the round's sender checksums and fullSync decisions on a side stream
-    // (one shard: k_ck_snapcopy, k_checksums_snap beside the ping merge,
-    // k_pending beside the response merge's pass 1)
-    bool ck_side = false;                      // the side stream exists (one shard)
-    // ... and this round uses it: fault runs (fail-stops, storms, partitions),
-    // whose distinct views make the checksum stage a few hundred long chains;
-    // without faults the stage is a handful of short ones and splitting the
-    // response merge around k_pending costs more than it hides
-    bool side_round() const { return ck_side && fault_mode; }
-    hipStream_t st2 = nullptr;
-    hipEvent_t ev_ck_copy = nullptr, ev_ck_done = nullptr, ev_merge_done = nullptr, ev_pend_done = nullptr;
-    uint32_t ck_cap = 0;                       // leader rows of the snapshot
-    DevBuf<uint64_t> ck_rows;                  // ck_cap x n view values
-    DevBuf<unsigned long long> ck_lfp;         // the leaders' fingerprints
-    DevBuf<uint32_t> ck_lres, ck_hlead;        // their checksums; leader index by fingerprint slot
-    double side_ms = 0;                        // device time of the side stream's work (timing on)
-    std::vector<TimedSpan> side_spans;
-    DevBuf<rp::Origin> origins;
-    DevBuf<unsigned long long> arena_cursor, stats, totals, fp_mm, bstats;
-    DevBuf<uint32_t> pt_hash;
-    // exchange (G > 1)
-    DevBuf<rp::PingMeta> meta;
-    DevBuf<uint64_t> soff, seoff, psoff, pseoff, rx_off, rx_eoff;
-    DevBuf<uint32_t> rr_idx, rs_idx, msg_nesc;
-    DevBuf<rp::RespRec> rsend, rrecv;
-    DevBuf<uint32_t> sendw, rxw, psendw, rx2w;  // cross-shard messages: words ...
-    DevBuf<rp::Esc> sende, rxe, psende, rx2e;  // ... and escapes (SimDev::rxw)
-    DevBuf<Change> rxc;                         // received pings, W3-W5 lists decoded (responses, W6: from rx2w)
-    DevBuf<unsigned long long> xcnt, sgather, xrow, ltotals;  // ltotals: this shard's own counters
-    DevBuf<uint32_t> gseen, gs_range, gsettled;
-    // ping-req waves across shards (k_xs_*)
-    DevBuf<uint8_t> pr_ckv;
-    DevBuf<uint32_t> w3cnt, w4b;  // k_pr_need's per-relay bounds
-    DevBuf<uint32_t> fdecl_bits, fdecl_count;
-    DevBuf<uint32_t> fdecl_all;  // G: every shard's k_fdecl_share, all-gathered (sharded fault rounds)
-    bool fd_shared = false;      // fdecl_all holds this round's counts
-    // a view may hold faulty or leave members no k_timers declared (views set
-    // from given statuses, changes applied through the node bridge): k_pr_need
-    // then bounds its relays' ring shrink by all n (k_pr_hist)
-    bool faulty_unbounded = false;
-    DevBuf<uint32_t> pq_nesc, rl_nesc, xs_rec, xs_w, xs_e, xs_list, xs_nlist, lorigin_count, lorigin_sent;
-    DevBuf<rp::Origin> og;  // origin all-gather: G blocks of 1 + og_cap records (k_origin_pack)
-    uint32_t og_cap = 0;
-    DevBuf<uint64_t> xs_wabs, xs_eabs;
-    DevBuf<rp::SlotRec> xsend, xrecv;
-    DevBuf<unsigned long long> xsrow;
-    unsigned long long* h_xsrow = nullptr;  // pinned: the all-gathered G x 3 x G send counts, then the pack count
-    unsigned long long* h_xcnt = nullptr;  // pinned: XC_NCAT x G counts of the round
-    unsigned long long* h_xrow = nullptr;  // pinned: G x 2 x G response payload counts (words, escapes)
-    uint32_t npts = 0, ncoll = 0, seen_words = 0;
-    bool join_mode = false;  // views may lack members: the JOIN merge kernels
-    bool life_mode = false;  // graceful leaves scheduled (with join_mode): k_iterate / k_round_end skip gossip-off nodes
-    DevBuf<uint32_t> life_ev, tcount;  // a round's events (k_lifecycle); k_timer_count's result
-    bool fault_mode = false;  // fail-stops, storms or partitions scheduled: the settled-filter issue kernels
-    bool issue_wave = RP_ISSUE_WAVE != 0;  // rp_sim_config.issue_wave: the one-wave issue kernels where eligible
-    // k_phase1 / k_p2_respond as one wave per node (wave_issue): runs without
-    // faults or joins, rows of whole 64-entry groups, a seen window that fits its LDS
-    bool wave_issue_ok() const {
-        return issue_wave && !fault_mode && !join_mode && n % 64 == 0 && seen_words <= rp::SEEN_STAGE_WORDS;
+void copy_batches(const std::vector<CopyDesc>& segs, hipStream_t st) {
+    for (size_t i0 = 0; i0 < segs.size(); i0 += COPY_BATCH) {
+        CopyBatch b{};
+        b.n = (uint32_t)std::min<size_t>(COPY_BATCH, segs.size() - i0);
+        uint64_t mx = 0;
+        for (uint32_t j = 0; j < b.n; j++) { b.d[j] = segs[i0 + j]; mx = std::max<uint64_t>(mx, b.d[j].bytes); }
+        const uint32_t gx = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(1, (mx + 65535) / 65536));
+        hipLaunchKernelGGL(k_copy_batch, dim3(gx, b.n), dim3(256), 0, st, b);
     }
-    // join replies of a round (rp_sim_join): per pair its seed's view, member
-    // order / count and checksum (filled on the seed's shard, then shared)
-    DevBuf<uint64_t> jvs;
-    DevBuf<uint32_t> jord, jm, jcs, j_ids, j_poff, j_pidx, j_pjoin, j_seedof;
-    DevBuf<int32_t> j_pseed;
-    std::vector<std::string> addrs;  // in sort order; preset by rp_sim_load_addresses, else the sim scheme
-    uint32_t timing = 0;  // bit cat: stage cat's spans are timed (rp_sim_enable_timing_stages)
-    uint64_t xsent = 0;  // bytes this shard sent to other shards (all-gathers, all-to-alls, all-reduces) since enable_timing
-    std::vector<TimedSpan> spans;
-    std::vector<hipEvent_t> ev_pool;  // recorded and collected events, reused (an event create costs a driver call)
-    double kms[NCAT] = {0, 0, 0, 0, 0, 0, 0};
-    uint64_t klaunch[NCAT] = {0, 0, 0, 0, 0, 0, 0};
+}
 
-    ~Shard() {
-        for (auto& s : spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
-        for (auto e : ev_pool) (void)hipEventDestroy(e);
-        if (h_xcnt) (void)hipHostFree(h_xcnt);
-        if (h_xrow) (void)hipHostFree(h_xrow);
-        if (h_xsrow) (void)hipHostFree(h_xsrow);
-        if (xev) (void)hipEventDestroy(xev);
-        for (hipEvent_t e : {ev_ck_copy, ev_ck_done, ev_merge_done, ev_pend_done})
-            if (e) (void)hipEventDestroy(e);
-        for (auto& sp : side_spans) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
-        if (st2) (void)hipStreamDestroy(st2);
-        if (st && own_stream) (void)hipStreamDestroy(st);
-    }
-    // side-stream work, timed on its own stream (kernel_ms "checksum_side")
-    template <class F>
-    void side_timed(F&& launch) {
-        if (!((timing >> 4) & 1u)) { launch(); return; }
-        TimedSpan sp{4, take_event(), take_event()};
-        RP_HIP(hipEventRecord(sp.a, st2));
-        launch();
-        RP_HIP(hipEventRecord(sp.b, st2));
-        side_spans.push_back(sp);
-    }
-
-    template <class F>
-    void timed(int cat, F&& launch) {
-        if (!((timing >> cat) & 1u)) { launch(); return; }
-        TimedSpan s{cat, take_event(), take_event()};
-        RP_HIP(hipEventRecord(s.a, st));
-        launch();
-        RP_HIP(hipEventRecord(s.b, st));
-        spans.push_back(s);
-    }
-    void collect_timing() {
-        for (auto& s : spans) {
-            float ms = 0;
-            RP_HIP(hipEventElapsedTime(&ms, s.a, s.b));
-            kms[s.cat] += ms;
-            klaunch[s.cat]++;
-            ev_pool.push_back(s.a);
-            ev_pool.push_back(s.b);
-        }
-        spans.clear();
-        for (auto& sp : side_spans) {
-            float ms = 0;
-            RP_HIP(hipEventElapsedTime(&ms, sp.a, sp.b));
-            side_ms += ms;
-            ev_pool.push_back(sp.a);
-            ev_pool.push_back(sp.b);
-        }
-        side_spans.clear();
-    }
-    // buffer resets queued for one k_fill_batch launch (fill_flush)
-    std::vector<rp::FillDesc> fills;
-    void fill(void* dst, uint64_t bytes, uint8_t byte) {
-        if (bytes % 4) throw Error(RP_ERR_STATE, "fill: size not a multiple of 4");
-        if (bytes) fills.push_back(rp::FillDesc{dst, bytes, byte * 0x01010101u, 0});
-    }
-    // seen_clear: the last batch also clears the round's seen bits (k_round_start)
-    void fill_flush(bool seen_clear = false) {
-        for (size_t i0 = 0; i0 < fills.size() || (seen_clear && i0 == 0); i0 += rp::FILL_BATCH) {
-            rp::FillBatch b{};
-            b.n = (uint32_t)std::min<size_t>(rp::FILL_BATCH, fills.size() - i0);
-            uint64_t mx = 0;
-            for (uint32_t j = 0; j < b.n; j++) { b.d[j] = fills[i0 + j]; mx = std::max<uint64_t>(mx, b.d[j].bytes); }
-            const uint32_t gx = (uint32_t)std::min<uint64_t>(256, std::max<uint64_t>(1, (mx / 4 + 255) / 256));
-            if (seen_clear && i0 + rp::FILL_BATCH >= fills.size())
-                hipLaunchKernelGGL(rp::k_round_start, dim3(gx * b.n + (nl + 3) / 4), dim3(256), 0, st, b, gx, d);
-            else
-                hipLaunchKernelGGL(rp::k_fill_batch, dim3(gx, b.n), dim3(256), 0, st, b);
-        }
-        fills.clear();
-    }
-    hipEvent_t take_event() {
-        hipEvent_t e = nullptr;
-        if (!ev_pool.empty()) { e = ev_pool.back(); ev_pool.pop_back(); return e; }
-        RP_HIP(hipEventCreate(&e));
-        return e;
-    }
-
-    void setup();
-    // prefilled: counts reset by stage_start; counted: and counted already (k_phase1, one shard)
-    void group(const int32_t* dest, uint32_t nslots, bool prefilled = false, bool counted = false);
-    // the pending fullSync decisions (k_pending)
-    void launch_pending(hipStream_t s) {
-        hipLaunchKernelGGL(rp::k_pending, dim3(std::min(rp::grid_for(d.snap_cap, rp::NWAVE), 8192u)), dim3(rp::BLOCK), 0,
-                           s, d);
-    }
-    // one round = these stages in order; a cluster exchanges between them
-    void stage_start(uint32_t round, bool churn_active, uint32_t slot, const std::vector<int32_t>& dead_now,
-                     bool faults, const uint32_t part[3], uint32_t storm_k);
-    void stage_churn(bool churn_active, uint32_t slot, uint32_t storm_k, uint64_t now);
-    // the set() bootstrap of nodes [node_lo, node_lo + count) from views (st/inc
-    // rows, or every member of member_map alive at INC0 + id) (rp_sim_set_views)
-    void bootstrap_views(uint32_t node_lo, uint32_t count, const uint8_t* st, const uint64_t* inc,
-                         const uint8_t* member_map, uint64_t seed);
-    void stage_issue();
-    void stage_checksums();
-    void stage_ping_merge(uint64_t now);
-    void stage_resp_merge(uint64_t now, bool faults);
-    void stage_pr_need();
-    void stage_wave(int w, uint64_t now);  // ping-req waves W3..W6 (faults)
-    void checksums(uint32_t* out, bool prefilled = false);  // ck_list's views -> out[v] (and the cache), one per distinct view
-    void ensure_ck_side();                 // the side stream's leader rows (allocated when faults are scheduled)
-    void checksums_side(uint32_t* out, bool prefilled = false);  // the same, the chains on st2 (ck_side; ready at ev_ck_done)
-    // exchange buffers sized to a round's traffic (escapes dominate once
-    // suspect/faulty updates circulate); direction 0: pings and W3/W4,
-    // 1: responses and W5/W6
-    void fit_exchange(int dir, uint64_t send_w, uint64_t send_e, uint64_t recv_w, uint64_t recv_e);
-    // every exchange buffer to at least e elements (rp_sim::presize_exchange)
-    void presize(uint64_t e) {
-        for (auto* b : {&sendw, &rxw, &psendw, &rx2w}) b->reserve(e);
-        for (auto* b : {&sende, &rxe, &psende, &rx2e}) b->reserve(e);
-        rxc.reserve(e);
-        d.rxw = rxw.p; d.rxe = rxe.p; d.rx2w = rx2w.p; d.rx2e = rx2e.p; d.rxc = rxc.p;
-    }
-    uint64_t xsum(int cat) const {
-        uint64_t t = 0;
-        for (uint32_t q = 0; q < G; q++) t += h_xcnt[(size_t)cat * G + q];
-        return t;
-    }
-    void stage_end();
-    uint32_t read_err();
-};
+void add_u32(uint32_t* dst, const uint32_t* src, size_t count, hipStream_t st) {
+    hipLaunchKernelGGL(k_add_u32, dim3(grid_for(count, 256)), dim3(256), 0, st, dst, src, (uint32_t)count);
+}
 
 // Every device pointer the round kernels dereference unconditionally, checked
 // on the host before the first launch: a field added to SimDev and never
@@ -7033,402 +6489,14 @@ uint32_t Shard::read_err() {
     return e;
 }
 
-}  // namespace
-
-
-// ---------------------------------------------------------------- rank transports
-// A process that holds one shard of a G-rank cluster exchanges with the other
-// ranks through a transport: RCCL (one process per GPU, rp_sim_create_rank),
-// or a loopback among the host threads of one process on one device
-// (rp_sim_create_rank_loop): the same rank code -- plans, counts, offsets,
-// buffer sizes -- with the collectives done as device copies, so that the
-// rank path runs and is compared with the in-process shards where one GPU is
-// all there is.
-namespace rp {
-struct Xfer {
-    uint32_t peer;
-    void* ptr;
-    size_t bytes;
-};
-struct Xport {
-    virtual ~Xport() = default;
-    // in place: this rank's chunk is base + rank * bytes, the others arrive
-    virtual void allgather(uint8_t* base, size_t bytes, uint32_t rank, hipStream_t st) = 0;
-    virtual void allreduce_u32(uint32_t* buf, size_t count, hipStream_t st) = 0;
-    // matching pairs: this rank's send to q is q's receive from this rank
-    virtual void sendrecv(const std::vector<Xfer>& sends, const std::vector<Xfer>& recvs, hipStream_t st) = 0;
-    virtual void broadcast(uint8_t* p, size_t bytes, uint32_t root, hipStream_t st) = 0;
-};
 }  // namespace rp
 
-#define RP_NCCL(expr)                                                                               \
-    do {                                                                                            \
-        ncclResult_t r_ = (expr);                                                                   \
-        if (r_ != ncclSuccess) throw Error(RP_ERR_HIP, std::string(#expr) + ": " + ncclGetErrorString(r_)); \
-    } while (0)
-
-namespace rp {
-struct NcclXport : Xport {
-    ncclComm_t comm = nullptr;
-    ~NcclXport() override { if (comm) (void)ncclCommDestroy(comm); }
-    void allgather(uint8_t* base, size_t bytes, uint32_t rank, hipStream_t st) override {
-        RP_NCCL(ncclAllGather(base + (size_t)rank * bytes, base, bytes, ncclUint8, comm, st));
-    }
-    void allreduce_u32(uint32_t* buf, size_t count, hipStream_t st) override {
-        RP_NCCL(ncclAllReduce(buf, buf, count, ncclUint32, ncclSum, comm, st));
-    }
-    void sendrecv(const std::vector<Xfer>& sends, const std::vector<Xfer>& recvs, hipStream_t st) override {
-        RP_NCCL(ncclGroupStart());
-        for (const Xfer& x : sends) RP_NCCL(ncclSend(x.ptr, x.bytes, ncclUint8, (int)x.peer, comm, st));
-        for (const Xfer& x : recvs) RP_NCCL(ncclRecv(x.ptr, x.bytes, ncclUint8, (int)x.peer, comm, st));
-        RP_NCCL(ncclGroupEnd());
-    }
-    void broadcast(uint8_t* p, size_t bytes, uint32_t root, hipStream_t st) override {
-        RP_NCCL(ncclBroadcast(p, p, bytes, ncclUint8, (int)root, comm, st));
-    }
-};
-
-// The loopback group: every collective is a rendezvous of all G rank threads.
-// Each rank posts its transfers and records an event after its earlier work;
-// the last rank to arrive leads: on the group's own stream it waits for every
-// rank's event, moves all G x (G - 1) segments with batched copy launches
-// (k_copy_batch, as the in-process exchanges do) and records one done event,
-// then releases the others; every rank's stream waits on that one event.  Per
-// collective that is 2 API calls per rank plus G + 2 for the leader, where a
-// copy and two waits per segment (~180 calls at G = 8, with eight threads
-// contending for the runtime) left the GPU idle a third of each round.
-struct LoopGroup {
-    uint32_t G;
-    std::mutex m;
-    std::condition_variable cv;
-    uint32_t arrived = 0;
-    uint64_t gen = 0;
-    bool broken = false;  // a rank threw: the others stop waiting
-    struct Post {
-        std::vector<Xfer> sends, recvs;
-        hipEvent_t ready = nullptr;
-    };
-    std::vector<Post> post;
-    hipStream_t xs = nullptr;    // the leader's copies (created by the first leader)
-    hipEvent_t done = nullptr;   // recorded on xs after each collective's copies
-    explicit LoopGroup(uint32_t g) : G(g), post(g) {}
-    ~LoopGroup() {
-        if (xs) (void)hipStreamSynchronize(xs);
-        if (done) (void)hipEventDestroy(done);
-        if (xs) (void)hipStreamDestroy(xs);
-    }
-    // true for the last rank to arrive, which then leads and calls release()
-    bool arrive() {
-        std::unique_lock<std::mutex> l(m);
-        if (broken) throw Error(RP_ERR_STATE, "loopback cluster: another rank failed");
-        const uint64_t g0 = gen;
-        if (++arrived == G) {
-            arrived = 0;
-            return true;
-        }
-        if (!cv.wait_for(l, std::chrono::seconds(120), [&] { return gen != g0 || broken; }) || broken) {
-            broken = true;
-            cv.notify_all();
-            throw Error(RP_ERR_STATE, "loopback cluster: a rank did not reach the collective");
-        }
-        return false;
-    }
-    void release() {
-        std::lock_guard<std::mutex> l(m);
-        gen++;
-        cv.notify_all();
-    }
-    void fail() {
-        std::lock_guard<std::mutex> l(m);
-        broken = true;
-        cv.notify_all();
-    }
-    // (the leader, all posts in) every receive matched to its send, the
-    // segments copied on xs once every rank's earlier work is done
-    void lead() {
-        if (!xs) {
-            RP_HIP(hipStreamCreateWithFlags(&xs, hipStreamNonBlocking));
-            RP_HIP(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-        }
-        for (const Post& p : post) RP_HIP(hipStreamWaitEvent(xs, p.ready, 0));
-        CopyBatch b{};
-        uint64_t mx = 0;
-        auto flush = [&] {
-            if (!b.n) return;
-            const uint32_t gx = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(1, (mx + 65535) / 65536));
-            hipLaunchKernelGGL(k_copy_batch, dim3(gx, b.n), dim3(256), 0, xs, b);
-            b.n = 0;
-            mx = 0;
-        };
-        size_t nsend = 0, nrecv = 0;
-        for (const Post& p : post) nsend += p.sends.size();
-        for (uint32_t r = 0; r < G; r++) {
-            for (const Xfer& x : post[r].recvs) {
-                const Xfer* src = nullptr;
-                for (const Xfer& y : post[x.peer].sends)
-                    if (y.peer == r) { src = &y; break; }
-                if (!src || src->bytes != x.bytes)
-                    throw Error(RP_ERR_STATE, "loopback cluster: a receive has no matching send");
-                nrecv++;
-                if (!x.bytes) continue;
-                b.d[b.n++] = CopyDesc{src->ptr, x.ptr, (uint64_t)x.bytes};
-                mx = std::max<uint64_t>(mx, x.bytes);
-                if (b.n == COPY_BATCH) flush();
-            }
-        }
-        if (nrecv != nsend) throw Error(RP_ERR_STATE, "loopback cluster: a send has no matching receive");
-        flush();
-        RP_HIP(hipGetLastError());
-        RP_HIP(hipEventRecord(done, xs));
-    }
-};
-
-struct LoopXport : Xport {
-    LoopGroup* g;
-    uint32_t rank;
-    hipEvent_t ready = nullptr;
-    DevBuf<uint32_t> stage, tmp;  // all-reduce: this rank's input, then every other rank's
-    LoopXport(LoopGroup* grp, uint32_t r) : g(grp), rank(r) {
-        RP_HIP(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
-    }
-    ~LoopXport() override {
-        if (ready) (void)hipEventDestroy(ready);
-    }
-    void exchange(const std::vector<Xfer>& sends, const std::vector<Xfer>& recvs, hipStream_t st) {
-        try {
-            RP_HIP(hipEventRecord(ready, st));
-            g->post[rank].sends = sends;
-            g->post[rank].recvs = recvs;
-            g->post[rank].ready = ready;
-            if (g->arrive()) {
-                try {
-                    g->lead();
-                } catch (...) {
-                    g->fail();
-                    throw;
-                }
-                g->release();
-            }
-            // (the posts are read by the leader before its release: this
-            // rank may post again once it is past here)
-            RP_HIP(hipStreamWaitEvent(st, g->done, 0));
-        } catch (...) {
-            g->fail();
-            throw;
-        }
-    }
-    void allgather(uint8_t* base, size_t bytes, uint32_t r, hipStream_t st) override {
-        std::vector<Xfer> sends, recvs;
-        for (uint32_t q = 0; q < g->G; q++)
-            if (q != r) {
-                sends.push_back(Xfer{q, base + (size_t)r * bytes, bytes});
-                recvs.push_back(Xfer{q, base + (size_t)q * bytes, bytes});
-            }
-        exchange(sends, recvs, st);
-    }
-    void allreduce_u32(uint32_t* buf, size_t count, hipStream_t st) override {
-        stage.reserve(count);
-        tmp.reserve(count * g->G);
-        RP_HIP(hipMemcpyAsync(stage.p, buf, count * 4, hipMemcpyDeviceToDevice, st));
-        std::vector<Xfer> sends, recvs;
-        for (uint32_t q = 0; q < g->G; q++)
-            if (q != rank) {
-                sends.push_back(Xfer{q, stage.p, count * 4});
-                recvs.push_back(Xfer{q, tmp.p + (size_t)q * count, count * 4});
-            }
-        exchange(sends, recvs, st);
-        for (uint32_t q = 0; q < g->G; q++)
-            if (q != rank)
-                hipLaunchKernelGGL(k_add_u32, dim3(grid_for(count, 256)), dim3(256), 0, st, buf,
-                                   (const uint32_t*)(tmp.p + (size_t)q * count), (uint32_t)count);
-    }
-    void sendrecv(const std::vector<Xfer>& sends, const std::vector<Xfer>& recvs, hipStream_t st) override {
-        exchange(sends, recvs, st);
-    }
-    void broadcast(uint8_t* p, size_t bytes, uint32_t root, hipStream_t st) override {
-        std::vector<Xfer> sends, recvs;
-        if (rank == root) {
-            for (uint32_t q = 0; q < g->G; q++)
-                if (q != root) sends.push_back(Xfer{q, p, bytes});
-        } else {
-            recvs.push_back(Xfer{root, p, bytes});
-        }
-        exchange(sends, recvs, st);
-    }
-};
-}  // namespace rp
-
-struct rp_loop {
-    rp::LoopGroup grp;
-    explicit rp_loop(uint32_t g) : grp(g) {}
-};
-
-// A simulated cluster: G shards of N/G nodes each.  Either all shards live in
-// this process on one device (exchanges are device copies; used by the tests
-// and for single-GPU runs, G = 1), or this process holds one shard of a
-// G-process cluster and exchanges over RCCL (one process per GPU).
-struct rp_sim {
-    rp_sim_config cfg{};
-    uint32_t n = 0, k = 0, G = 1;
-    int dev = 0;  // the HIP device it lives on (entry points may come from any host thread)
-    std::vector<std::unique_ptr<Shard>> sh;  // local shards (all G, or one)
-    std::unique_ptr<rp::Xport> comm;         // RCCL (or loopback): this process holds shard `rank` only
-    uint32_t rank = 0;
-    hipStream_t st = nullptr;                // shared by in-process shards
-    std::vector<int32_t> fail_round;         // per node: round of its fail-stop, -1 none
-    struct JoinEv { uint32_t round, joiner; std::vector<int32_t> seeds; };
-    std::vector<JoinEv> joins;               // rp_sim_join's schedule, in order
-    std::vector<int32_t> join_round;         // per node: round it joins at, -1 = a member from the start
-    // rp_sim_leave / rp_sim_rejoin: per node the rounds of its events, strictly
-    // increasing, leave (even index) and rejoin (odd) in turn; by round, the
-    // events (node, bit 31: a rejoin) in call order
-    std::vector<std::vector<uint32_t>> life;
-    std::map<uint32_t, std::vector<uint32_t>> life_at;
-    // the node's gossip runs during round r: a function of the schedule, like
-    // live_at (an event before the node's join is skipped)
-    bool gossiping_at(uint32_t i, uint32_t r) const {
-        if (life.empty()) return true;
-        bool on = true;
-        const std::vector<uint32_t>& e = life[i];
-        for (size_t j = 0; j < e.size() && e[j] <= r; j++)
-            if (join_round[i] < 0 || e[j] >= (uint32_t)join_round[i]) on = (j & 1) != 0;
-        return on;
-    }
-    // neither failed nor still outside the cluster at round r, and gossiping:
-    // the nodes churn and storms draw from
-    bool live_at(uint32_t i, uint32_t r) const {
-        return (fail_round[i] < 0 || (uint32_t)fail_round[i] > r) && (join_round[i] < 0 || (uint32_t)join_round[i] <= r) &&
-               gossiping_at(i, r);
-    }
-    void schedule_life(uint32_t node, uint32_t r, bool rejoin);
-    void join_step(uint32_t r, uint64_t now);
-    void life_step(uint32_t r, uint64_t now);
-    bool faults = false;
-    bool views_set = false;                  // rp_sim_set_views ran (rp_sim_load_addresses must come first)
-    uint32_t part[3] = {0, 0, 0};
-    uint64_t churn_rng = 0;
-    uint32_t round = 0;
-    int32_t* h_churn = nullptr;              // pinned staging for churn ids
-    // false-suspicion storm: rounds [start, end), ceil(live * ppm / 1e6) victims per round
-    uint32_t storm_start = 0, storm_end = 0, storm_ppm = 0, storm_kmax = 0;
-    uint64_t storm_rng = 0;
-    int32_t* h_storm = nullptr;              // pinned staging: CHURN_SLOTS x 2 x storm_kmax
-    std::vector<uint32_t> storm_k;           // pairs per staged round
-    uint64_t xbytes = 0, xcalls = 0;         // bytes this process sent in exchanges
-    // request routing (rp_sim_ring_checksums / rp_sim_route): the shards'
-    // ring_csum buffers are recomputed when an entry point that can change a
-    // ring ran since (host flag only: the round kernels know nothing of it);
-    // the per-shard pointer table and the bucket directory over the point
-    // hashes are built on first use and dropped with the shards
-    // (rp_sim_load_addresses)
-    bool ring_csum_stale = true;
-    DevBuf<rp::RouteShard> route_tab;
-    DevBuf<uint32_t> route_dir;
-    uint32_t route_dir_shift = 32;
-    void refresh_ring_checksums();
-    void route_prepare(bool checksums = true);
-    // ownership census (rp_sim_ownership / rp_sim_ownership_at; DESIGN.md
-    // §13): the same cache rule with a flag of its own -- the counts per
-    // interval, per node and the stats stay until an entry point that can
-    // change a ring ran.  The server -> point index and the shards' dead
-    // arrays are built on first use and dropped with the shards.
-    bool own_stale = true;
-    DevBuf<uint32_t> own_srv_pt, own_claims;
-    DevBuf<int32_t> own_diff, own_tile;
-    DevBuf<unsigned long long> own_claimed, own_out;
-    DevBuf<const uint8_t*> own_dead;
-    rp_ownership_stats own_stats{};
-    rp::OwnArgs own_args();
-    void own_refresh();
-    template <bool UNIFORM>
-    void route_launch(const uint32_t* entries, const uint32_t* keys, uint64_t seed, uint64_t count, int32_t* dests,
-                      uint8_t* outcomes, uint8_t* agrees, rp_route_stats* stats);
-
-    // f(shard) for every shard this process holds, in shard order.  (One host
-    // thread per in-process shard was measured: no faster, and it varied
-    // more -- 39.6-75 against 39.1-39.3 ms/round at 65,536 nodes on 4 shards.)
-    template <class F>
-    void each(F&& f) {
-        for (auto& s : sh) f(*s);
-    }
-
-    ~rp_sim() {
-        sh.clear();
-        if (xdone) (void)hipEventDestroy(xdone);
-        comm.reset();
-        if (h_churn) (void)hipHostFree(h_churn);
-        if (h_storm) (void)hipHostFree(h_storm);
-        if (st) (void)hipStreamDestroy(st);
-    }
-    Shard& owner_of(uint32_t node) {
-        for (auto& s : sh)
-            if (node - s->lo < s->nl) return *s;
-        throw Error(RP_ERR_INVALID, "node " + std::to_string(node) + " is not held by this process");
-    }
-    void choose_churn(int32_t* out, uint32_t r);
-    uint32_t choose_storm(int32_t* out, uint32_t r);
-    void enqueue_round(bool churn_active, uint32_t slot);
-    void run(int k_rounds, bool churn_active);
-    void check_errors();
-    // exchanges
-    template <class T>
-    void allgather_nodes(DevBuf<T> Shard::*buf, size_t per_node);
-    template <class T>
-    void allgather_block(DevBuf<T> Shard::*buf, size_t per_shard);
-    void allreduce_sum(DevBuf<uint32_t> Shard::*buf, size_t count);
-    void alltoallv(DevBuf<Change> Shard::*sendb, DevBuf<Change> Shard::*recvb, int cat_send, int cat_recv,
-                   size_t elem);
-    template <class T>
-    void alltoallv_t(DevBuf<T> Shard::*sendb, DevBuf<T> Shard::*recvb, int cat_send, int cat_recv);
-    void read_counts();
-    void origin_exchange();
-    template <int W>
-    void slot_exchange();
-    void sync_all() { for (auto& s : sh) RP_HIP(hipStreamSynchronize(s->st)); }
-    bool presized = false;
-    bool loop_rank = false;  // a loopback rank: its G - 1 peers share this device
-    void presize_exchange();
-    // In-process clusters run each shard on a stream of its own, so that the
-    // shards' kernels overlap as one-GPU-per-shard ranks would; an exchange
-    // step (device copies on the cluster stream st) starts after every
-    // shard's earlier work (xbegin) and every shard's later work waits for it
-    // (xend).  One shard per process (RCCL): the shard's stream orders both.
-    hipEvent_t xdone = nullptr;
-    // segment copies of the current in-process exchange (k_copy_batch at xend)
-    std::vector<rp::CopyDesc> cbatch;
-    void copy(void* dst, const void* src, size_t bytes) {
-        if (bytes) cbatch.push_back(rp::CopyDesc{src, dst, (uint64_t)bytes});
-    }
-    void copy_flush() {
-        for (size_t i0 = 0; i0 < cbatch.size(); i0 += rp::COPY_BATCH) {
-            rp::CopyBatch b{};
-            b.n = (uint32_t)std::min<size_t>(rp::COPY_BATCH, cbatch.size() - i0);
-            uint64_t mx = 0;
-            for (uint32_t j = 0; j < b.n; j++) { b.d[j] = cbatch[i0 + j]; mx = std::max<uint64_t>(mx, b.d[j].bytes); }
-            const uint32_t gx = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(1, (mx + 65535) / 65536));
-            hipLaunchKernelGGL(rp::k_copy_batch, dim3(gx, b.n), dim3(256), 0, st, b);
-        }
-        cbatch.clear();
-    }
-    bool overlap() const { return !comm && sh.size() > 1 && sh.front()->st != st; }
-    // (nested scopes: consecutive collectives with no shard work between
-    // them share one ordering step and one copy launch)
-    int xdepth = 0;
-    void xbegin() {
-        if (xdepth++ > 0 || !overlap()) return;
-        for (auto& s : sh) {
-            RP_HIP(hipEventRecord(s->xev, s->st));
-            RP_HIP(hipStreamWaitEvent(st, s->xev, 0));
-        }
-    }
-    void xend() {
-        if (--xdepth > 0) return;
-        copy_flush();
-        if (!overlap()) return;
-        RP_HIP(hipEventRecord(xdone, st));
-        for (auto& s : sh) RP_HIP(hipStreamWaitEvent(s->st, xdone, 0));
-    }
-};
+using rp::CHURN_SLOTS;
+using rp::Change;
+using rp::DevBuf;
+using rp::Error;
+using rp::NCAT;
+using rp::Shard;
 
 // Every shard's slice [lo, lo + nl) of a per-node array -> every shard.
 template <class T>
@@ -7485,8 +6553,7 @@ void rp_sim::allreduce_sum(DevBuf<uint32_t> Shard::*buf, size_t count) {
     Shard& s0 = *sh[0];
     xbegin();
     for (size_t i = 1; i < sh.size(); i++)
-        hipLaunchKernelGGL(rp::k_add_u32, dim3(rp::grid_for(count, 256)), dim3(256), 0, st, (s0.*buf).p,
-                           (const uint32_t*)(sh[i].get()->*buf).p, (uint32_t)count);
+        rp::add_u32((s0.*buf).p, (sh[i].get()->*buf).p, count, st);
     for (size_t i = 1; i < sh.size(); i++) {
         copy((sh[i].get()->*buf).p, (s0.*buf).p, count * 4);
         sh[i]->xsent += count * 4;  // (its part in, the sum back)
@@ -7825,8 +6892,7 @@ void rp_sim::schedule_life(uint32_t node, uint32_t r, bool rejoin) {
     if (!e.empty() && r <= e.back()) throw Error(RP_ERR_INVALID, "a node's events come in strictly increasing rounds");
     e.push_back(r);
     life_at[r].push_back(node | (rejoin ? 0x80000000u : 0u));
-    ring_csum_stale = true;
-    own_stale = true;
+    rings_changed();
     faults = true;
     for (auto& s : sh) { s->join_mode = true; s->life_mode = true; s->faulty_unbounded = true; }
     presize_exchange();
@@ -8027,178 +7093,6 @@ void rp_sim::presize_exchange() {
     sync_all();
 }
 
-// ---- request routing -----------------------------------------
-// Every local view's ring checksum into its shard's ring_csum, unless no call
-// that can change a ring ran since the last time (timed as "checksum").
-void rp_sim::refresh_ring_checksums() {
-    bool have = !ring_csum_stale;
-    for (auto& s : sh) have = have && s->ring_csum.p;
-    if (have) return;
-    for (auto& sp : sh) {
-        Shard& s = *sp;
-        if (!s.ring_csum.p) {
-            s.ring_csum.alloc(s.n);
-            RP_HIP(hipMemsetAsync(s.ring_csum.p, 0, s.ring_csum.bytes(), s.st));
-        }
-        s.timed(4, [&] {
-            hipLaunchKernelGGL(rp::k_ring_checksums, dim3(std::min(rp::grid_for(s.nl, rp::NWAVE), 8192u)), dim3(rp::BLOCK),
-                               0, s.st, s.d, s.ring_csum.p);
-        });
-        RP_HIP(hipGetLastError());
-    }
-    ring_csum_stale = false;
-}
-
-// What a route needs besides the simulation state: fresh ring checksums, the
-// shards' base pointers and the bucket directory (about one point per bucket).
-void rp_sim::route_prepare(bool checksums) {
-    if (comm)
-        throw Error(RP_ERR_UNSUPPORTED, "routing needs every node's view: not available on one rank of a multi-process "
-                                        "or loop cluster");
-    RP_HIP(hipSetDevice(dev));
-    check_errors();
-    if (checksums) refresh_ring_checksums();
-    // (the census reads no checksum, but the pointer table below names the buffers)
-    for (auto& s : sh)
-        if (!s->ring_csum.p) {
-            s->ring_csum.alloc(s->n);
-            RP_HIP(hipMemsetAsync(s->ring_csum.p, 0, s->ring_csum.bytes(), s->st));
-        }
-    Shard& s0 = *sh.front();
-    if (!route_dir.p) {
-        uint32_t bits = 0;
-        while (bits < 22 && (2ull << bits) <= s0.npts) bits++;
-        const uint32_t nb = 1u << bits;
-        route_dir.alloc((size_t)nb + 1);
-        route_dir_shift = 32 - bits;
-        hipLaunchKernelGGL(rp::k_route_dir, dim3(rp::grid_for((uint64_t)nb + 1, 256)), dim3(256), 0, s0.st,
-                           (const uint32_t*)s0.pt_hash.p, s0.npts, route_dir_shift, nb, route_dir.p);
-        RP_HIP(hipGetLastError());
-    }
-    if (!route_tab.p) {
-        std::vector<rp::RouteShard> h;
-        for (auto& s : sh) h.push_back(rp::RouteShard{s->in_ring.p, s->coll_owner.p, s->ring_count.p, s->ring_csum.p});
-        route_tab.alloc(h.size());
-        RP_HIP(hipMemcpy(route_tab.p, h.data(), h.size() * sizeof(rp::RouteShard), hipMemcpyHostToDevice));
-    }
-    sync_all();  // the route reads every shard's rows from the first shard's stream
-}
-
-template <bool UNIFORM>
-void rp_sim::route_launch(const uint32_t* entries, const uint32_t* keys, uint64_t seed, uint64_t count, int32_t* dests,
-                          uint8_t* outcomes, uint8_t* agrees, rp_route_stats* stats) {
-    Shard& s0 = *sh.front();
-    rp::SimDev S = s0.d;
-    S.round = round;  // the clock of the next round, as the wire bridge
-    S.part_start = part[0]; S.part_end = part[1]; S.part_split = part[2];
-    DevBuf<unsigned long long> dst(rp::ROUTE_NCOUNT);
-    RP_HIP(hipMemsetAsync(dst.p, 0, dst.bytes(), s0.st));
-    // (launches of at most 2^31 requests: a thread's counters are 32-bit)
-    for (uint64_t first = 0; first < count; first += 1ull << 31) {
-        const uint64_t m = std::min<uint64_t>(count - first, 1ull << 31);
-        s0.timed(5, [&] {
-            hipLaunchKernelGGL(rp::k_route<UNIFORM>, dim3(std::min(rp::grid_for(m, 256), 16384u)), dim3(256), 0, s0.st, S,
-                               (const rp::RouteShard*)route_tab.p, (const uint32_t*)s0.pt_hash.p,
-                               (const int32_t*)s0.pt_server.p, (const int32_t*)s0.pt_coll.p, s0.npts,
-                               (const uint32_t*)route_dir.p, route_dir_shift, UNIFORM ? nullptr : entries + first,
-                               UNIFORM ? nullptr : keys + first, seed, first, m, dests ? dests + first : nullptr,
-                               outcomes ? outcomes + first : nullptr, agrees ? agrees + first : nullptr, dst.p);
-        });
-        RP_HIP(hipGetLastError());
-    }
-    unsigned long long h[rp::ROUTE_NCOUNT];
-    RP_HIP(hipMemcpyAsync(h, dst.p, sizeof h, hipMemcpyDeviceToHost, s0.st));
-    RP_HIP(hipStreamSynchronize(s0.st));
-    if (stats) {
-        stats->local = h[rp::ROUTE_LOCAL];
-        stats->delivered = h[rp::ROUTE_DELIVERED];
-        stats->checksums_differ = h[rp::ROUTE_CHECKSUMS_DIFFER];
-        stats->unreachable = h[rp::ROUTE_UNREACHABLE];
-        stats->entry_dead = h[rp::ROUTE_ENTRY_DEAD];
-        stats->misrouted = h[rp::ROUTE_MISROUTED];
-        stats->requests = stats->local + stats->delivered + stats->checksums_differ + stats->unreachable + stats->entry_dead;
-        stats->reserved = 0;
-    }
-}
-
-// ---- ownership census -----------------------------------------
-// (after route_prepare(false): the pointer table and the directory exist)
-rp::OwnArgs rp_sim::own_args() {
-    Shard& s0 = *sh.front();
-    rp::OwnArgs A{};
-    A.tab = route_tab.p;
-    A.dead = own_dead.p;
-    A.pt_hash = s0.pt_hash.p; A.pt_server = s0.pt_server.p; A.pt_coll = s0.pt_coll.p;
-    A.dir = route_dir.p;
-    A.srv_pt = own_srv_pt.p;
-    A.n = n; A.nl = s0.nl; A.ncoll = s0.ncoll; A.npts = s0.npts; A.dir_shift = route_dir_shift;
-    A.ntiles = (s0.npts + rp::OWN_TILE - 1) / rp::OWN_TILE;
-    A.diff = own_diff.p; A.claims = own_claims.p; A.tile_sum = own_tile.p;
-    A.claimed = own_claimed.p; A.out = own_out.p;
-    return A;
-}
-
-// The census, unless no call that can change a ring ran since the last one
-// (timed as "other", like a route).  Runs on the first shard's stream.
-void rp_sim::own_refresh() {
-    route_prepare(false);
-    Shard& s0 = *sh.front();
-    const uint32_t npts = s0.npts;
-    if (!own_dead.p) {
-        std::vector<const uint8_t*> h;
-        for (auto& s : sh) h.push_back(s->dead.p);
-        own_dead.alloc(h.size());
-        RP_HIP(hipMemcpy(own_dead.p, h.data(), h.size() * sizeof h[0], hipMemcpyHostToDevice));
-    }
-    if (!own_srv_pt.p) {
-        // every server's replica hashes as the constructor made them, each
-        // row sorted: the device search turns them into point indices
-        std::string blob;
-        std::vector<uint64_t> off{0};
-        for (const std::string& a : s0.addrs) { blob += a; off.push_back(blob.size()); }
-        std::vector<uint32_t> rep;
-        rp::device_replica_hashes(blob, off, rp::REPLICAS, rep, s0.st);
-        if (cfg.replica_hash_shift)
-            for (auto& h : rep) h = (h >> cfg.replica_hash_shift) << cfg.replica_hash_shift;
-        for (size_t sv = 0; sv < n; sv++) std::sort(rep.begin() + sv * rp::REPLICAS, rep.begin() + (sv + 1) * rp::REPLICAS);
-        DevBuf<uint32_t> dh(rep.size()), idx(rep.size());
-        RP_HIP(hipMemcpyAsync(dh.p, rep.data(), rep.size() * 4, hipMemcpyHostToDevice, s0.st));
-        rp::own_point_index(s0.st, own_args(), dh.p, idx.p);
-        RP_HIP(hipGetLastError());
-        RP_HIP(hipStreamSynchronize(s0.st));
-        own_srv_pt = std::move(idx);  // (kept only once it is complete)
-        own_stale = true;
-    }
-    if (!own_stale && own_claims.n == npts && own_claimed.n == n) return;
-    if (own_diff.n != (size_t)npts + 1) own_diff.alloc((size_t)npts + 1);
-    if (own_claims.n != npts) own_claims.alloc(npts);
-    if (own_claimed.n != n) own_claimed.alloc(n);
-    if (!own_out.p) own_out.alloc(rp::OWN_NOUT);
-    const uint32_t ntiles = (npts + rp::OWN_TILE - 1) / rp::OWN_TILE;
-    if (own_tile.n != ntiles) own_tile.alloc(ntiles);
-    const rp::OwnArgs A = own_args();
-    s0.timed(5, [&] {
-        RP_HIP(hipMemsetAsync(own_diff.p, 0, own_diff.bytes(), s0.st));
-        RP_HIP(hipMemsetAsync(own_out.p, 0, own_out.bytes(), s0.st));
-        rp::own_census(s0.st, A);
-    });
-    RP_HIP(hipGetLastError());
-    unsigned long long h[rp::OWN_NOUT];
-    RP_HIP(hipMemcpyAsync(h, own_out.p, sizeof h, hipMemcpyDeviceToHost, s0.st));
-    RP_HIP(hipStreamSynchronize(s0.st));
-    rp_ownership_stats st{};
-    for (int k = 0; k < 8; k++) st.measure[k] = h[rp::OWN_MEASURE + k];
-    st.claimants = h[rp::OWN_CLAIMANTS];
-    st.intervals = npts;
-    st.max_claims = h[rp::OWN_MAX] >> 32;
-    const uint32_t first = ~(uint32_t)h[rp::OWN_MAX];
-    uint32_t hash = 0;
-    if (first < npts) RP_HIP(hipMemcpy(&hash, s0.pt_hash.p + first, 4, hipMemcpyDeviceToHost));
-    st.max_claims_hash = hash;
-    own_stats = st;
-    own_stale = false;
-}
-
 void rp_sim::check_errors() {
     uint32_t e = 0;
     for (auto& s : sh) e |= s->read_err();
@@ -8280,128 +7174,23 @@ int rp_sim_create_shards(const rp_sim_config* cfg, int nshards, rp_sim** out) {
     });
 }
 
-int rp_comm_unique_id(uint8_t* id, size_t cap) {
-    return rp::guarded([&] {
-        if (!id || cap < sizeof(ncclUniqueId)) throw Error(RP_ERR_INVALID, "id buffer must hold 128 bytes");
-        ncclUniqueId u;
-        RP_NCCL(ncclGetUniqueId(&u));
-        memcpy(id, &u, sizeof u);
-    });
-}
-
 int rp_sim_create_rank(const rp_sim_config* cfg, int nranks, int rank, const uint8_t* id, rp_sim** out) {
     return rp::guarded([&] {
         if (!out || !id || nranks < 1 || rank < 0 || rank >= nranks) throw Error(RP_ERR_INVALID, "bad argument");
-        std::unique_ptr<rp::NcclXport> x;
+        std::unique_ptr<rp::Xport> x;
         if (nranks > 1) {
             RP_HIP(hipSetDevice(rp::current_device()));
-            ncclUniqueId u;
-            memcpy(&u, id, sizeof u);
-            x.reset(new rp::NcclXport());
-            RP_NCCL(ncclCommInitRank(&x->comm, nranks, u, rank));
+            x = rp::nccl_xport(nranks, rank, id);
         }
         *out = make_cluster(cfg, (uint32_t)nranks, nranks > 1 ? rank : -1, std::move(x));
     });
 }
 
-// The RCCL transport on its own (rp::NcclXport, the four calls the rank path
-// makes), on small buffers whose contents every rank can predict: rank r's
-// all-gather chunk, all-reduce input and sends are functions of (r, peer, i).
-// nranks = 1 runs every call on one GPU (the sends and receives go to the
-// rank itself), so the library's RCCL linkage, communicator set-up and call
-// arguments are exercised where only one GPU is available.
-static uint32_t selftest_word(uint32_t from, uint32_t to, uint32_t i) {
-    return 0x9E3779B1u * (from + 1) ^ 0x85EBCA6Bu * (to + 7) ^ (i * 2654435761u);
-}
-int rp_comm_selftest(int nranks, int rank, const uint8_t* id, uint32_t words, uint32_t* failures) {
-    return rp::guarded([&] {
-        if (!id || !failures || nranks < 1 || rank < 0 || rank >= nranks || words == 0 || words > (1u << 24))
-            throw Error(RP_ERR_INVALID, "bad argument");
-        RP_HIP(hipSetDevice(rp::current_device()));
-        rp::NcclXport x;
-        ncclUniqueId u;
-        memcpy(&u, id, sizeof u);
-        RP_NCCL(ncclCommInitRank(&x.comm, nranks, u, rank));
-        const uint32_t G = (uint32_t)nranks, r = (uint32_t)rank, W = words;
-        struct StreamGuard {  // (destroyed on every exit, a throw included)
-            hipStream_t s = nullptr;
-            ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
-        } sg;
-        RP_HIP(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
-        const hipStream_t st = sg.s;
-        DevBuf<uint32_t> ag, ar, sb, rb;
-        ag.alloc((size_t)G * W); ar.alloc(W); sb.alloc((size_t)G * W); rb.alloc((size_t)G * W);
-        std::vector<uint32_t> h((size_t)G * W, 0u);
-        // all-gather in place: this rank's chunk at base + r * bytes
-        for (uint32_t i = 0; i < W; i++) h[(size_t)r * W + i] = selftest_word(r, rp::NONE, i);
-        RP_HIP(hipMemcpyAsync(ag.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));
-        x.allgather((uint8_t*)ag.p, (size_t)W * 4, r, st);
-        // all-reduce (sum) of u32
-        std::vector<uint32_t> a(W);
-        for (uint32_t i = 0; i < W; i++) a[i] = selftest_word(r, 0, i) & 0xFFFFu;
-        RP_HIP(hipMemcpyAsync(ar.p, a.data(), (size_t)W * 4, hipMemcpyHostToDevice, st));
-        x.allreduce_u32(ar.p, W, st);
-        // one grouped send/recv with every rank (itself included), a
-        // different length per pair as the exchanges have
-        std::vector<uint32_t> sbh((size_t)G * W);
-        std::vector<rp::Xfer> sends, recvs;
-        for (uint32_t q = 0; q < G; q++) {
-            const uint32_t len_s = W - (r + 2 * q) % W, len_r = W - (q + 2 * r) % W;
-            for (uint32_t i = 0; i < W; i++) sbh[(size_t)q * W + i] = selftest_word(r, q, i);
-            sends.push_back(rp::Xfer{q, sb.p + (size_t)q * W, (size_t)len_s * 4});
-            recvs.push_back(rp::Xfer{q, rb.p + (size_t)q * W, (size_t)len_r * 4});
-        }
-        RP_HIP(hipMemcpyAsync(sb.p, sbh.data(), sbh.size() * 4, hipMemcpyHostToDevice, st));
-        RP_HIP(hipMemsetAsync(rb.p, 0, (size_t)G * W * 4, st));
-        x.sendrecv(sends, recvs, st);
-        std::vector<uint32_t> hag((size_t)G * W), har(W), hrb((size_t)G * W), hbc(W);
-        RP_HIP(hipMemcpyAsync(hag.data(), ag.p, hag.size() * 4, hipMemcpyDeviceToHost, st));
-        RP_HIP(hipMemcpyAsync(har.data(), ar.p, har.size() * 4, hipMemcpyDeviceToHost, st));
-        RP_HIP(hipMemcpyAsync(hrb.data(), rb.p, hrb.size() * 4, hipMemcpyDeviceToHost, st));
-        // broadcast from the last rank (reuses ar on the device; the payload
-        // has a host vector of its own, so the pageable all-reduce input
-        // copied above is never rewritten while that copy may be pending)
-        const uint32_t root = G - 1;
-        std::vector<uint32_t> bc(W, 0u);
-        if (r == root)
-            for (uint32_t i = 0; i < W; i++) bc[i] = selftest_word(root, root, i);
-        RP_HIP(hipMemcpyAsync(ar.p, bc.data(), (size_t)W * 4, hipMemcpyHostToDevice, st));
-        x.broadcast((uint8_t*)ar.p, (size_t)W * 4, root, st);
-        RP_HIP(hipMemcpyAsync(hbc.data(), ar.p, hbc.size() * 4, hipMemcpyDeviceToHost, st));
-        RP_HIP(hipStreamSynchronize(st));
-        uint32_t bad = 0;
-        for (uint32_t q = 0; q < G; q++)
-            for (uint32_t i = 0; i < W; i++) {
-                bad += hag[(size_t)q * W + i] != selftest_word(q, rp::NONE, i);
-                const uint32_t len_r = W - (q + 2 * r) % W;
-                bad += hrb[(size_t)q * W + i] != (i < len_r ? selftest_word(q, r, i) : 0u);
-            }
-        for (uint32_t i = 0; i < W; i++) {
-            uint32_t want = 0;
-            for (uint32_t q = 0; q < G; q++) want += selftest_word(q, 0, i) & 0xFFFFu;
-            bad += har[i] != want;
-            bad += hbc[i] != selftest_word(root, root, i);
-        }
-        *failures = bad;
-    });
-}
-
-int rp_loop_create(int nranks, rp_loop** out) {
-    return rp::guarded([&] {
-        if (!out || nranks < 2 || nranks > (int)rp::MAXG) throw Error(RP_ERR_INVALID, "nranks must be in [2, 64]");
-        *out = new rp_loop((uint32_t)nranks);
-    });
-}
-int rp_loop_destroy(rp_loop* g) {
-    delete g;
-    return RP_OK;
-}
 int rp_sim_create_rank_loop(const rp_sim_config* cfg, rp_loop* group, int rank, rp_sim** out) {
     return rp::guarded([&] {
-        if (!out || !group || rank < 0 || rank >= (int)group->grp.G) throw Error(RP_ERR_INVALID, "bad argument");
+        if (!out || !group || rank < 0 || rank >= (int)rp::loop_ranks(group)) throw Error(RP_ERR_INVALID, "bad argument");
         RP_HIP(hipSetDevice(rp::current_device()));
-        std::unique_ptr<rp::Xport> x(new rp::LoopXport(&group->grp, (uint32_t)rank));
-        *out = make_cluster(cfg, group->grp.G, rank, std::move(x));
+        *out = make_cluster(cfg, rp::loop_ranks(group), rank, rp::loop_xport(group, rank));
         (*out)->loop_rank = true;
     });
 }
@@ -8421,8 +7210,7 @@ int rp_sim_destroy(rp_sim* s) {
 int rp_sim_run(rp_sim* s, int k_rounds, int churn_active) {
     return rp::guarded([&] {
         if (!s || k_rounds < 0) throw Error(RP_ERR_INVALID, "bad argument");
-        s->ring_csum_stale = true;
-        s->own_stale = true;
+        s->rings_changed();
         s->run(k_rounds, churn_active != 0);
     });
 }
@@ -8457,8 +7245,7 @@ int rp_sim_node_flags(rp_sim* c, uint32_t node, uint32_t* flags) {
     return rp::guarded([&] {
         if (!c || node >= c->n || !flags) throw Error(RP_ERR_INVALID, "bad argument");
         RP_HIP(hipSetDevice(c->dev));
-        c->ring_csum_stale = true;
-        c->own_stale = true;
+        c->rings_changed();
         c->check_errors();
         Shard* s = &c->owner_of(node);
         uint8_t g = 0, q = 0;
@@ -8482,9 +7269,10 @@ int rp_sim_load_addresses(rp_sim* s, const uint8_t* bytes, const uint64_t* off, 
         if (s->views_set || !s->joins.empty() || !s->life.empty())
             throw Error(RP_ERR_STATE,
                         "addresses must be loaded before rp_sim_set_views / rp_sim_join / rp_sim_leave / rp_sim_rejoin");
-        // (new shards, new points: the routing tables go with the old ones)
-        s->ring_csum_stale = true;
-        s->own_stale = true;
+        // (new shards, new points: the routing tables go with the old ones.
+        // own_refresh relies on this order: the server -> point index is
+        // dropped nowhere else, so a census that rebuilds it is stale already)
+        s->rings_changed();
         s->route_tab.release();
         s->route_dir.release();
         s->own_srv_pt.release();
@@ -8525,8 +7313,7 @@ int rp_sim_set_views(rp_sim* s, uint32_t node_lo, uint32_t count, const int32_t*
         if (s->round != 0) throw Error(RP_ERR_STATE, "views can only be set before the first round");
         if ((uint64_t)node_lo + count > s->n) throw Error(RP_ERR_INVALID, "node range outside the cluster");
         if (!count) return;
-        s->ring_csum_stale = true;
-        s->own_stale = true;
+        s->rings_changed();
         const uint32_t n = s->n;
         std::vector<uint8_t> st((size_t)count * n);
         std::vector<uint64_t> inc((size_t)count * n);
@@ -8573,8 +7360,7 @@ int rp_sim_join(rp_sim* s, const uint32_t* joiners, const uint32_t* rounds, cons
         if (!s || (count && (!joiners || !rounds || (seeds_per && !seeds)))) throw Error(RP_ERR_INVALID, "null pointer");
         if (s->round != 0) throw Error(RP_ERR_STATE, "joins can only be scheduled before the first round");
         if (!s->joins.empty()) throw Error(RP_ERR_STATE, "the join schedule is already set");
-        s->ring_csum_stale = true;
-        s->own_stale = true;
+        s->rings_changed();
         const uint32_t n = s->n;
         std::vector<int32_t> jr(n, -1);
         for (uint32_t i = 0; i < count; i++) {
@@ -8678,8 +7464,7 @@ static void read_stats(rp_sim* c, const unsigned long long* src, rp_round_stats*
 int rp_sim_round(rp_sim* s, int churn_active, rp_round_stats* stats) {
     return rp::guarded([&] {
         if (!s) throw Error(RP_ERR_INVALID, "null sim");
-        s->ring_csum_stale = true;
-        s->own_stale = true;
+        s->rings_changed();
         s->run(1, churn_active != 0);
         s->check_errors();
         if (stats) read_stats(s, s->sh.front()->stats.p, stats, true);
@@ -8870,8 +7655,7 @@ int rp_sim_handle_ping(rp_sim* c, uint32_t node, int64_t source, uint64_t source
                        uint32_t* applied, int* full_sync) {
     return rp::guarded([&] {
         Shard& s = bridge_shard(c, node);
-        c->ring_csum_stale = true;
-        c->own_stale = true;
+        c->rings_changed();
         if (source < -1 || source >= (int64_t)c->n) throw Error(RP_ERR_INVALID, "bad source");
         // the response (a list or a fullSync) holds at most n changes: check
         // the buffer before the update and the issue change any state
@@ -8906,8 +7690,7 @@ int rp_sim_handle_ping(rp_sim* c, uint32_t node, int64_t source, uint64_t source
 int rp_sim_update(rp_sim* c, uint32_t node, const rp_change* changes, uint32_t n, uint32_t* applied) {
     return rp::guarded([&] {
         Shard& s = bridge_shard(c, node);
-        c->ring_csum_stale = true;
-        c->own_stale = true;
+        c->rings_changed();
         const uint32_t a = bridge_apply(s, node, changes, n, rp::T0 + rp::PERIOD_MS * c->round);
         bridge_done(c, s);
         if (applied) *applied = a;
@@ -9042,84 +7825,6 @@ int rp_sim_ring_lookup(rp_sim* c, uint32_t node, const uint32_t* key_hashes, siz
     });
 }
 
-int rp_sim_ring_checksums(rp_sim* c, uint32_t* out, size_t cap) {
-    return rp::guarded([&] {
-        if (!c || !out) throw Error(RP_ERR_INVALID, "null pointer");
-        if (cap < c->n) throw Error(RP_ERR_INVALID, "checksum buffer holds fewer than n entries");
-        RP_HIP(hipSetDevice(c->dev));
-        memset(out, 0, (size_t)c->n * 4);  // nodes of other processes' shards stay 0
-        c->refresh_ring_checksums();
-        for (auto& s : c->sh) {
-            RP_HIP(hipMemcpyAsync(out + s->lo, s->ring_csum.p + s->lo, (size_t)s->nl * 4, hipMemcpyDeviceToHost, s->st));
-            RP_HIP(hipStreamSynchronize(s->st));
-        }
-    });
-}
-
-int rp_sim_route(rp_sim* c, const uint32_t* entries, const uint32_t* key_hashes, size_t nk, int32_t* dests,
-                 uint8_t* outcomes, uint8_t* owner_agrees, rp_route_stats* stats) {
-    return rp::guarded([&] {
-        if (!c || (nk && (!entries || !key_hashes))) throw Error(RP_ERR_INVALID, "null pointer");
-        for (size_t i = 0; i < nk; i++)
-            if (entries[i] >= c->n) throw Error(RP_ERR_INVALID, "request " + std::to_string(i) + ": entry node out of range");
-        c->route_prepare();
-        if (stats) memset(stats, 0, sizeof *stats);
-        if (nk == 0) return;
-        Shard& s0 = *c->sh.front();
-        DevBuf<uint32_t> de(nk), dh(nk);
-        DevBuf<int32_t> dd(dests ? nk : 0);
-        DevBuf<uint8_t> dout(outcomes ? nk : 0), dag(owner_agrees ? nk : 0);
-        RP_HIP(hipMemcpyAsync(de.p, entries, nk * 4, hipMemcpyHostToDevice, s0.st));
-        RP_HIP(hipMemcpyAsync(dh.p, key_hashes, nk * 4, hipMemcpyHostToDevice, s0.st));
-        c->route_launch<false>(de.p, dh.p, 0, nk, dd.p, dout.p, dag.p, stats);  // (ends with the stream drained)
-        if (dests) RP_HIP(hipMemcpyAsync(dests, dd.p, nk * 4, hipMemcpyDeviceToHost, s0.st));
-        if (outcomes) RP_HIP(hipMemcpyAsync(outcomes, dout.p, nk, hipMemcpyDeviceToHost, s0.st));
-        if (owner_agrees) RP_HIP(hipMemcpyAsync(owner_agrees, dag.p, nk, hipMemcpyDeviceToHost, s0.st));
-        RP_HIP(hipStreamSynchronize(s0.st));
-    });
-}
-
-int rp_sim_route_uniform(rp_sim* c, uint64_t seed, uint64_t count, rp_route_stats* stats) {
-    return rp::guarded([&] {
-        if (!c || !stats) throw Error(RP_ERR_INVALID, "null pointer");
-        c->route_prepare();
-        memset(stats, 0, sizeof *stats);
-        if (count) c->route_launch<true>(nullptr, nullptr, seed, count, nullptr, nullptr, nullptr, stats);
-    });
-}
-
-int rp_sim_ownership(rp_sim* c, rp_ownership_stats* stats, uint64_t* claimed, size_t cap) {
-    return rp::guarded([&] {
-        if (!c || !stats) throw Error(RP_ERR_INVALID, "null pointer");
-        if (claimed && cap < c->n) throw Error(RP_ERR_INVALID, "claimed buffer holds fewer than n entries");
-        c->own_refresh();
-        static_assert(sizeof(rp_ownership_stats) == 128, "rp_ownership_stats is 16 x u64");
-        *stats = c->own_stats;
-        if (claimed) RP_HIP(hipMemcpy(claimed, c->own_claimed.p, (size_t)c->n * 8, hipMemcpyDeviceToHost));
-    });
-}
-
-int rp_sim_ownership_at(rp_sim* c, const uint32_t* key_hashes, size_t nk, uint32_t* claims) {
-    return rp::guarded([&] {
-        if (!c || (nk && (!key_hashes || !claims))) throw Error(RP_ERR_INVALID, "null pointer");
-        c->own_refresh();
-        if (nk == 0) return;
-        Shard& s0 = *c->sh.front();
-        const rp::OwnArgs A = c->own_args();
-        // (launches of at most 2^30 keys: a thread's index is 32-bit)
-        const size_t chunk = std::min<size_t>(nk, (size_t)1 << 30);
-        DevBuf<uint32_t> dh(chunk), dc(chunk);
-        for (size_t first = 0; first < nk; first += chunk) {
-            const size_t m = std::min(nk - first, chunk);
-            RP_HIP(hipMemcpyAsync(dh.p, key_hashes + first, m * 4, hipMemcpyHostToDevice, s0.st));
-            s0.timed(5, [&] { rp::own_at(s0.st, A, dh.p, (uint32_t)m, dc.p); });
-            RP_HIP(hipGetLastError());
-            RP_HIP(hipMemcpyAsync(claims + first, dc.p, m * 4, hipMemcpyDeviceToHost, s0.st));
-            RP_HIP(hipStreamSynchronize(s0.st));
-        }
-    });
-}
-
 int rp_sim_address(rp_sim* c, uint32_t node, char* buf, size_t cap) {
     if (!c || node >= c->n || !buf) return RP_ERR_INVALID;
     const std::string& a = c->sh.front()->addrs[node];
@@ -9199,363 +7904,6 @@ int rp_sim_exchange_stats(rp_sim* c, double* ms, uint64_t* bytes_sent, uint64_t*
     if (bytes_sent) *bytes_sent = c->xbytes;
     if (rounds) *rounds = c->xcalls;
     return RP_OK;
-}
-
-}  // extern "C"
-
-// =====================================================================
-// Request traffic with proxy retries across rounds (rp_traffic_*; DESIGN.md
-// §11).  A tracker keeps its request table on its simulation's device and
-// runs on the first shard's stream, like a route.
-// =====================================================================
-struct rp_traffic {
-    rp_sim* sim = nullptr;
-    rp_traffic_config cfg{};
-    uint64_t lifetime = 0;             // rounds a request can stay pending: the delays of its max_retries retries
-    DevBuf<uint4> tab[2];              // the pending table and the buffer the next compaction writes (2 words a record)
-    int cur = 0;
-    uint64_t alloc = 0;                // records each holds (<= cfg.capacity)
-    DevBuf<uint4> stage;               // a submitted chunk's surviving records, tile by tile
-    DevBuf<uint32_t> tile_count, tile_off, ctl;
-    DevBuf<unsigned long long> cum, hist;
-    uint64_t hist_rows = 0;
-    DevBuf<uint4> results;             // by id (tracking)
-    uint64_t results_cap = 0;
-    uint64_t next_id = 0, run_index = 0;
-    uint64_t bound = 0;                // >= the device's pending count
-    uint32_t h_ctl[rp::TC_NWORDS] = {0};
-    struct Span { int cat; hipEvent_t a, b; };
-    std::vector<Span> spans;           // cfg.timing: 0 poll, 1 submit
-    double ms[2] = {0, 0};
-    uint64_t calls[2] = {0, 0};
-    static constexpr uint64_t CHUNK = 1ull << 20;  // requests per submit launch
-
-    hipStream_t st() const { return sim->sh.front()->st; }
-    ~rp_traffic() {
-        for (auto& s : spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
-    }
-
-    // `count` elements with the first `keep` kept and the rest set to `fill` bytes
-    template <class T>
-    void grow(DevBuf<T>& b, uint64_t count, uint64_t keep, int fill) {
-        DevBuf<T> nb((size_t)count);
-        if (keep) RP_HIP(hipMemcpyAsync(nb.p, b.p, (size_t)keep * sizeof(T), hipMemcpyDeviceToDevice, st()));
-        if (count > keep) RP_HIP(hipMemsetAsync(nb.p + keep, fill, (size_t)(count - keep) * sizeof(T), st()));
-        RP_HIP(hipStreamSynchronize(st()));
-        b = std::move(nb);
-    }
-    // room for `need` pending records, or RP_ERR_CAPACITY (nothing changed)
-    void ensure_table(uint64_t need) {
-        if (need > cfg.capacity)
-            throw Error(RP_ERR_CAPACITY, "the pending table would need " + std::to_string(need) + " records, capacity is " +
-                                             std::to_string(cfg.capacity));
-        if (need > alloc) {
-            const uint64_t na = std::min<uint64_t>(cfg.capacity, std::max<uint64_t>({need, alloc * 2, 1024}));
-            grow(tab[cur], 2 * na, 2 * bound, 0);
-            tab[cur ^ 1].alloc((size_t)(2 * na));
-            alloc = na;
-        }
-        const uint64_t tiles = (std::max(alloc, CHUNK) + rp::TRAFFIC_TILE - 1) / rp::TRAFFIC_TILE;
-        if (tile_count.n < tiles) { tile_count.alloc((size_t)tiles); tile_off.alloc((size_t)tiles); }
-    }
-    void ensure_history(uint64_t rows) {
-        if (rows <= hist_rows) return;
-        const uint64_t nr = std::max<uint64_t>({rows, hist_rows * 2, 64});
-        grow(hist, nr * rp::TS_NSTATS, hist_rows * rp::TS_NSTATS, 0);
-        hist_rows = nr;
-    }
-    void ensure_results(uint64_t ids) {
-        if (!cfg.track || ids <= results_cap) return;
-        const uint64_t nr = std::max<uint64_t>({ids, results_cap * 2, 1024});
-        grow(results, nr, results_cap, 0xFF);
-        results_cap = nr;
-    }
-    void ensure_stage(uint64_t n) {
-        const uint64_t m = std::min(n, CHUNK);
-        if (stage.n < 2 * m) stage.alloc((size_t)(2 * m));
-    }
-    // the control words; a survivor that found no room is an error (the table is presized: never expected)
-    void read_ctl() {
-        RP_HIP(hipMemcpyAsync(h_ctl, ctl.p, sizeof h_ctl, hipMemcpyDeviceToHost, st()));
-        RP_HIP(hipStreamSynchronize(st()));
-        bound = h_ctl[rp::TC_COUNT];
-        if (h_ctl[rp::TC_OVERFLOW]) throw Error(RP_ERR_STATE, "the pending table overflowed on the device");
-    }
-    // fresh ring checksums and routing tables, then the pending count
-    void prepare() {
-        sim->route_prepare();
-        read_ctl();
-    }
-    rp::TrafficArgs args() {
-        Shard& s0 = *sim->sh.front();
-        rp::TrafficArgs A{};
-        A.tab = sim->route_tab.p;
-        A.pt_hash = s0.pt_hash.p; A.pt_server = s0.pt_server.p; A.pt_coll = s0.pt_coll.p;
-        A.dir = sim->route_dir.p;
-        A.npts = s0.npts; A.dir_shift = sim->route_dir_shift;
-        A.max_retries = (uint32_t)cfg.max_retries; A.nschedule = cfg.nschedule;
-        A.enforce = cfg.enforce_consistency ? 1u : 0u;
-        for (uint32_t i = 0; i < rp::TRAFFIC_MAX_SCHEDULE; i++) A.schedule[i] = cfg.schedule[i];
-        A.cum = cum.p;
-        A.row = hist.p + (size_t)sim->round * rp::TS_NSTATS;
-        A.results = results.p; A.results_cap = results_cap;
-        A.ctl = ctl.p;
-        A.tile_count = tile_count.p; A.tile_off = tile_off.p;
-        A.tiles_cap = (uint32_t)tile_count.n;
-        return A;
-    }
-    rp::SimDev clocked() {
-        rp::SimDev S = sim->sh.front()->d;
-        S.round = sim->round;  // the clock of the next round, as a route
-        S.part_start = sim->part[0]; S.part_end = sim->part[1]; S.part_split = sim->part[2];
-        return S;
-    }
-    template <class F>
-    void timed(int cat, F&& launch) {
-        if (!cfg.timing) { launch(); return; }
-        Span s{cat, nullptr, nullptr};
-        RP_HIP(hipEventCreate(&s.a));
-        RP_HIP(hipEventCreate(&s.b));
-        RP_HIP(hipEventRecord(s.a, st()));
-        launch();
-        RP_HIP(hipEventRecord(s.b, st()));
-        spans.push_back(s);
-    }
-    static unsigned tile_grid(uint64_t records) {
-        return std::min(rp::grid_for(std::max<uint64_t>(records, 1), rp::TRAFFIC_TILE), 8192u);
-    }
-    // every due pending record retries; the survivors, in order, become the table (history row presized)
-    void launch_poll() {
-        if (!alloc) return;  // nothing was ever submitted
-        const rp::TrafficArgs A = args();
-        const rp::SimDev S = clocked();
-        const uint32_t cap = (uint32_t)alloc;
-        timed(0, [&] {
-            rp::traffic_step(rp::TRAFFIC_PENDING, tile_grid(bound), st(), S, A, tab[cur].p, cap, nullptr, nullptr, 0, 0, 0, 0);
-            rp::traffic_scan(false, st(), A, 0, cap, cap);
-            rp::traffic_scatter(false, tile_grid(bound), st(), A, tab[cur].p, tab[cur ^ 1].p, 0, cap, cap);
-        });
-        RP_HIP(hipGetLastError());
-        cur ^= 1;
-    }
-    // first attempts of n requests (device arrays, or the generator from index `first`); survivors are appended
-    void launch_submit(const uint32_t* entries, const uint32_t* keys, uint64_t seed, uint64_t first, uint64_t n) {
-        const rp::TrafficArgs A = args();
-        const rp::SimDev S = clocked();
-        const uint32_t cap_stage = (uint32_t)(stage.n / 2), cap = (uint32_t)alloc;
-        timed(1, [&] {
-            for (uint64_t off = 0; off < n; off += CHUNK) {
-                const uint32_t m = (uint32_t)std::min(n - off, CHUNK);
-                rp::traffic_step(entries ? rp::TRAFFIC_BATCH : rp::TRAFFIC_UNIFORM, tile_grid(m), st(), S, A, stage.p, cap_stage,
-                                 entries ? entries + off : nullptr, entries ? keys + off : nullptr, seed, first + off,
-                                 next_id + off, m);
-                rp::traffic_scan(true, st(), A, m, cap_stage, cap);
-                rp::traffic_scatter(true, tile_grid(m), st(), A, stage.p, tab[cur].p, m, cap_stage, cap);
-            }
-        });
-        RP_HIP(hipGetLastError());
-        next_id += n;
-    }
-    void submit(const uint32_t* d_entries, const uint32_t* d_keys, uint64_t seed, uint64_t first, uint64_t n) {
-        ensure_table(bound + n);
-        ensure_results(next_id + n);
-        ensure_history((uint64_t)sim->round + 1);
-        ensure_stage(n);
-        launch_submit(d_entries, d_keys, seed, first, n);
-        read_ctl();
-    }
-    void collect_timing() {
-        RP_HIP(hipStreamSynchronize(st()));
-        for (auto& s : spans) {
-            float t = 0;
-            RP_HIP(hipEventElapsedTime(&t, s.a, s.b));
-            ms[s.cat] += t;
-            calls[s.cat]++;
-            (void)hipEventDestroy(s.a);
-            (void)hipEventDestroy(s.b);
-        }
-        spans.clear();
-    }
-};
-
-extern "C" {
-
-int rp_traffic_create(rp_sim* sim, const rp_traffic_config* cfg, rp_traffic** out) {
-    return rp::guarded([&] {
-        if (!sim || !out) throw Error(RP_ERR_INVALID, "null pointer");
-        if (sim->comm)
-            throw Error(RP_ERR_UNSUPPORTED, "request traffic needs every node's view: not available on one rank of a "
-                                            "multi-process or loop cluster");
-        RP_HIP(hipSetDevice(sim->dev));
-        std::unique_ptr<rp_traffic> t(new rp_traffic());
-        t->sim = sim;
-        rp_traffic_config c{};
-        c.max_retries = -1;
-        c.enforce_consistency = -1;
-        if (cfg) c = *cfg;
-        if (c.max_retries < 0) c.max_retries = 3;
-        if (c.enforce_consistency < 0) c.enforce_consistency = 1;
-        if (c.nschedule == 0) {
-            // RETRY_SCHEDULE [0, 1, 3.5] s (send.js:49) in 200 ms periods, rounded up
-            c.nschedule = 3;
-            c.schedule[0] = 0; c.schedule[1] = 5; c.schedule[2] = 18;
-        }
-        if (c.capacity == 0) c.capacity = 1ull << 20;
-        if (c.max_retries > (int32_t)(rp::TS_RETRY_SLOTS - 1)) throw Error(RP_ERR_INVALID, "max_retries is at most 8");
-        if (c.nschedule > rp::TRAFFIC_MAX_SCHEDULE) throw Error(RP_ERR_INVALID, "the schedule has at most 8 entries");
-        if (c.capacity > (1ull << 30)) throw Error(RP_ERR_INVALID, "capacity is at most 2^30 records");
-        for (uint32_t i = 0; i < c.nschedule; i++)
-            if (c.schedule[i] > (1u << 20)) throw Error(RP_ERR_INVALID, "a retry delay is at most 2^20 rounds");
-        for (uint32_t i = c.nschedule; i < rp::TRAFFIC_MAX_SCHEDULE; i++) c.schedule[i] = 0;
-        t->cfg = c;
-        for (int32_t r = 0; r < c.max_retries; r++) t->lifetime += c.schedule[std::min<uint32_t>((uint32_t)r, c.nschedule - 1)];
-        t->ctl.alloc(rp::TC_NWORDS);
-        t->cum.alloc(64);
-        RP_HIP(hipMemsetAsync(t->ctl.p, 0, t->ctl.bytes(), t->st()));
-        RP_HIP(hipMemsetAsync(t->cum.p, 0, t->cum.bytes(), t->st()));
-        RP_HIP(hipStreamSynchronize(t->st()));
-        *out = t.release();
-    });
-}
-
-int rp_traffic_destroy(rp_traffic* t) {
-    return rp::guarded([&] {
-        delete t;  // (its buffers only: hipFree waits for the device; the simulation is not touched)
-    });
-}
-
-int rp_traffic_submit(rp_traffic* t, const uint32_t* entries, const uint32_t* key_hashes, size_t n, uint64_t* first_id) {
-    return rp::guarded([&] {
-        if (!t || (n && (!entries || !key_hashes))) throw Error(RP_ERR_INVALID, "null pointer");
-        for (size_t i = 0; i < n; i++)
-            if (entries[i] >= t->sim->n) throw Error(RP_ERR_INVALID, "request " + std::to_string(i) + ": entry node out of range");
-        t->prepare();
-        if (first_id) *first_id = t->next_id;
-        if (n == 0) return;
-        t->ensure_table(t->bound + n);  // (RP_ERR_CAPACITY before anything is copied or changed)
-        DevBuf<uint32_t> de(n), dh(n);
-        RP_HIP(hipMemcpyAsync(de.p, entries, n * 4, hipMemcpyHostToDevice, t->st()));
-        RP_HIP(hipMemcpyAsync(dh.p, key_hashes, n * 4, hipMemcpyHostToDevice, t->st()));
-        t->submit(de.p, dh.p, 0, 0, n);  // (ends with the stream drained)
-    });
-}
-
-int rp_traffic_submit_uniform(rp_traffic* t, uint64_t seed, uint64_t first, uint64_t count) {
-    return rp::guarded([&] {
-        if (!t) throw Error(RP_ERR_INVALID, "null tracker");
-        t->prepare();
-        if (count) t->submit(nullptr, nullptr, seed, first, count);
-    });
-}
-
-int rp_traffic_poll(rp_traffic* t) {
-    return rp::guarded([&] {
-        if (!t) throw Error(RP_ERR_INVALID, "null tracker");
-        t->prepare();
-        t->ensure_history((uint64_t)t->sim->round + 1);
-        t->launch_poll();
-        t->read_ctl();
-    });
-}
-
-int rp_traffic_run(rp_traffic* t, int k_rounds, int churn_active, uint64_t per_round, uint64_t seed) {
-    return rp::guarded([&] {
-        if (!t || k_rounds < 0) throw Error(RP_ERR_INVALID, "bad argument");
-        RP_HIP(hipSetDevice(t->sim->dev));
-        t->read_ctl();
-        // a batch stays at most `lifetime` rounds: at most that many earlier batches beside the newest
-        const uint64_t batches = std::min<uint64_t>((uint64_t)k_rounds, t->lifetime + 1);
-        if (per_round && batches > (1ull << 31) / per_round) throw Error(RP_ERR_CAPACITY, "per_round x rounds overflows");
-        const uint64_t need = t->bound + per_round * batches;
-        if (per_round || t->bound) t->ensure_table(need);
-        t->ensure_results(t->next_id + per_round * (uint64_t)k_rounds);
-        t->ensure_history((uint64_t)t->sim->round + (uint64_t)k_rounds + 1);
-        t->ensure_stage(per_round);
-        uint64_t host_bound = t->bound;
-        for (int r = 0; r < k_rounds; r++) {
-            t->sim->ring_csum_stale = true;
-            t->sim->own_stale = true;
-            t->sim->run(1, churn_active != 0);
-            t->sim->route_prepare();  // (rp_sim_round's error check; no other readback)
-            t->bound = host_bound;
-            t->launch_poll();
-            if (per_round) {
-                t->launch_submit(nullptr, nullptr, seed, t->run_index, per_round);
-                t->run_index += per_round;
-                host_bound = std::min(need, host_bound + per_round);
-            }
-        }
-        t->read_ctl();
-    });
-}
-
-int rp_traffic_read_stats(rp_traffic* t, rp_traffic_stats* cumulative, uint64_t* by_retries) {
-    return rp::guarded([&] {
-        if (!t) throw Error(RP_ERR_INVALID, "null tracker");
-        RP_HIP(hipSetDevice(t->sim->dev));
-        unsigned long long h[64];
-        RP_HIP(hipMemcpyAsync(h, t->cum.p, sizeof h, hipMemcpyDeviceToHost, t->st()));
-        RP_HIP(hipStreamSynchronize(t->st()));
-        static_assert(sizeof(rp_traffic_stats) == rp::TS_NSTATS * 8, "rp_traffic_stats is 16 x u64");
-        if (cumulative) memcpy(cumulative, h, sizeof *cumulative);
-        if (by_retries)
-            for (uint32_t i = 0; i < rp::TS_NOUTCOMES * rp::TS_RETRY_SLOTS; i++) by_retries[i] = h[rp::TS_NSTATS + i];
-    });
-}
-
-int rp_traffic_history(rp_traffic* t, uint32_t first_clock, uint32_t count, rp_traffic_stats* rows) {
-    return rp::guarded([&] {
-        if (!t || (count && !rows)) throw Error(RP_ERR_INVALID, "null pointer");
-        RP_HIP(hipSetDevice(t->sim->dev));
-        if (!count) return;
-        memset(rows, 0, (size_t)count * sizeof *rows);  // (clocks without a call: zero rows)
-        if (first_clock >= t->hist_rows) return;
-        const uint64_t m = std::min<uint64_t>(count, t->hist_rows - first_clock);
-        RP_HIP(hipMemcpyAsync(rows, t->hist.p + (size_t)first_clock * rp::TS_NSTATS, (size_t)m * sizeof *rows,
-                              hipMemcpyDeviceToHost, t->st()));
-        RP_HIP(hipStreamSynchronize(t->st()));
-    });
-}
-
-int rp_traffic_pending(rp_traffic* t, rp_request_pending* out, size_t cap, uint64_t* count) {
-    return rp::guarded([&] {
-        if (!t) throw Error(RP_ERR_INVALID, "null tracker");
-        RP_HIP(hipSetDevice(t->sim->dev));
-        t->read_ctl();
-        if (count) *count = t->bound;
-        if (!out) return;
-        if (cap < t->bound) throw Error(RP_ERR_INVALID, "pending buffer too small");
-        static_assert(sizeof(rp_request_pending) == 32, "a pending record is two 16-byte words");
-        if (t->bound)
-            RP_HIP(hipMemcpyAsync(out, t->tab[t->cur].p, (size_t)t->bound * 32, hipMemcpyDeviceToHost, t->st()));
-        RP_HIP(hipStreamSynchronize(t->st()));
-    });
-}
-
-int rp_traffic_results(rp_traffic* t, uint64_t first_id, size_t n, rp_request_result* out) {
-    return rp::guarded([&] {
-        if (!t || (n && !out)) throw Error(RP_ERR_INVALID, "null pointer");
-        if (!t->cfg.track) throw Error(RP_ERR_INVALID, "the tracker was created without `track`");
-        if (first_id > t->next_id || n > t->next_id - first_id) throw Error(RP_ERR_INVALID, "ids beyond the last submitted");
-        RP_HIP(hipSetDevice(t->sim->dev));
-        static_assert(sizeof(rp_request_result) == 16, "a final record is one 16-byte word");
-        if (n) RP_HIP(hipMemcpyAsync(out, t->results.p + first_id, n * 16, hipMemcpyDeviceToHost, t->st()));
-        RP_HIP(hipStreamSynchronize(t->st()));
-    });
-}
-
-int rp_traffic_times(rp_traffic* t, double* ms2, uint64_t* calls2, uint64_t* peak_pending) {
-    return rp::guarded([&] {
-        if (!t) throw Error(RP_ERR_INVALID, "null tracker");
-        RP_HIP(hipSetDevice(t->sim->dev));
-        t->collect_timing();
-        t->read_ctl();
-        for (int i = 0; i < 2; i++) {
-            if (ms2) ms2[i] = t->ms[i];
-            if (calls2) calls2[i] = t->calls[i];
-        }
-        if (peak_pending) *peak_pending = t->h_ctl[rp::TC_PEAK];
-    });
 }
 
 }  // extern "C"

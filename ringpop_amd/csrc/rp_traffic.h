@@ -1,9 +1,10 @@
-// ringpop_amd — request traffic with proxy retries across rounds (rp_traffic_*;
-// DESIGN.md §11): what the host side (rp_sim.hip) and the kernels that advance
-// the device-resident request table (rp_traffic.hip) share, and the ring walk
-// and bucket search that k_route (rp_sim.hip) and k_traffic_step both use.
-// The traffic kernels are a translation unit of their own, so that the code
-// object of the round kernels does not change with them.
+// ringpop_amd — what the kernels that walk a view's ring between rounds share:
+// k_route (rp_route.hip), the request tracker's k_traffic_step
+// (rp_traffic.hip; §11) and the ownership census (rp_own.hip; §13).  The
+// per-shard pointer table, the ring walk and the bucket search.  Each of those
+// features is a translation unit of its own, kernels and host side together,
+// so that the code object of the round kernels (rp_sim.hip) does not change
+// with them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -12,7 +13,6 @@
 
 namespace rp {
 
-// ---- shared with k_route
 // What a route reads of one shard's rings.  In-process shards keep their
 // nodes' rows in buffers of their own on one device: node v's are at row
 // v % nl of shard v / nl.
@@ -56,57 +56,5 @@ __device__ inline RouteRing route_ring_of(const SimDev& S, const RouteShard& t, 
     const size_t r = v % S.nl;
     return RouteRing{t.in_ring + r * S.n, t.coll_owner + r * S.ncoll};
 }
-
-// ---- the request table
-
-// rp_traffic_stats, then by_retries[outcome][0..8]
-enum : uint32_t {
-    TS_SUBMITTED = 0, TS_LOCAL = 1, TS_DELIVERED = 2, TS_REROUTED_LOCAL = 3, TS_FAILED = 4, TS_ENTRY_DEAD = 5,
-    TS_PROXIED = 6, TS_SEND_UNREACHABLE = 7, TS_CHECKSUMS_DIFFER = 8, TS_RETRY_SCHEDULED = 9, TS_RETRY_ATTEMPTED = 10,
-    TS_RETRY_REROUTED = 11, TS_RETRY_SUCCEEDED = 12, TS_RETRY_FAILED = 13, TS_MISROUTED = 14, TS_RESERVED = 15,
-    TS_NSTATS = 16, TS_NREG = 15, TS_RETRY_SLOTS = 9, TS_NOUTCOMES = 5, TS_NSLOTS = TS_NSTATS + TS_NOUTCOMES * TS_RETRY_SLOTS
-};
-enum : uint32_t { TO_LOCAL = 0, TO_DELIVERED = 1, TO_REROUTED_LOCAL = 2, TO_FAILED = 3, TO_ENTRY_DEAD = 4, TO_PENDING = 255 };
-// control words of a tracker (device): the pending count, the count the last
-// compaction started from, where the last batch's survivors were appended,
-// an overflow flag (a survivor that found no room: the host presizes the
-// table, so it stays 0) and the largest pending count seen
-enum : uint32_t { TC_COUNT = 0, TC_PREV = 1, TC_BASE = 2, TC_OVERFLOW = 3, TC_PEAK = 4, TC_NWORDS = 8 };
-constexpr uint32_t TRAFFIC_TILE = 256;
-constexpr uint32_t TRAFFIC_SCAN = 1024;
-constexpr uint32_t TRAFFIC_MAX_SCHEDULE = 8;
-
-// A pending record is two 16-byte words (rp_request_pending):
-//   {id lo, id hi, entry, key_hash} {first_dest, due, submit_clock, retries}
-// A final record is one (rp_request_result):
-//   {dest, outcome | retries << 8, submit_clock, done_clock}
-struct TrafficArgs {
-    const RouteShard* tab;
-    const uint32_t* pt_hash;
-    const int32_t* pt_server;
-    const int32_t* pt_coll;
-    const uint32_t* dir;
-    uint32_t npts, dir_shift;
-    uint32_t max_retries, nschedule, enforce;
-    uint32_t schedule[TRAFFIC_MAX_SCHEDULE];
-    unsigned long long* cum;  // TS_NSLOTS cumulative counters
-    unsigned long long* row;  // TS_NSTATS: the clock's history row
-    uint4* results;           // by id, or null (not tracking)
-    uint64_t results_cap;
-    uint32_t* ctl;            // TC_*
-    uint32_t* tile_count;     // survivors per tile of 256 records
-    uint32_t* tile_off;       // their exclusive prefix sums
-    uint32_t tiles_cap;
-};
-
-enum : int { TRAFFIC_PENDING = 0, TRAFFIC_BATCH = 1, TRAFFIC_UNIFORM = 2 };
-
-// launches on `st` (rp_traffic.hip); mode: TRAFFIC_*
-void traffic_step(int mode, unsigned grid, hipStream_t st, const SimDev& S, const TrafficArgs& A, uint4* recs, uint32_t cap,
-                  const uint32_t* entries, const uint32_t* keys, uint64_t seed, uint64_t first_index, uint64_t first_id,
-                  uint32_t count);
-void traffic_scan(bool append, hipStream_t st, const TrafficArgs& A, uint32_t count, uint32_t cap_src, uint32_t cap_table);
-void traffic_scatter(bool append, unsigned grid, hipStream_t st, const TrafficArgs& A, const uint4* src, uint4* dst,
-                     uint32_t count, uint32_t cap_src, uint32_t cap_dst);
 
 }  // namespace rp

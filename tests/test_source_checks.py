@@ -54,3 +54,17 @@ def test_build_tracks_every_header():
         if f.endswith(".h"):
             assert f in listed, f"{f} is not tracked by build.py"
     assert os.path.normpath(os.path.join("..", "..", "include", "ringpop_hip.h")) in listed
+
+
+def test_build_compiles_every_source():
+    """The counterpart for translation units: every *.hip in csrc/ is in
+    build.py's SOURCES (tools/build_variant.sh takes its list from there), so
+    a new file cannot be left out of the library, and every listed file
+    exists."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("rp_build", os.path.join(os.path.dirname(CSRC), "build.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    on_disk = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
+    assert on_disk == sorted(b.SOURCES)
+    assert len(set(b.SOURCES)) == len(b.SOURCES)
