@@ -472,6 +472,55 @@ typedef struct {
 int rp_sim_ownership(rp_sim *sim, rp_ownership_stats *stats, uint64_t *claimed, size_t cap);
 int rp_sim_ownership_at(rp_sim *sim, const uint32_t *key_hashes, size_t n, uint32_t *claims);
 
+/* ---- Ownership movement between two instants ---------------------------------
+ * Which keys changed hands.  A snapshot fixes, at the clock it
+ * is taken (rounds run so far), the claim set C(v) of every node v: the
+ * intervals v claims under the census' definition -- none for a node that is
+ * no claimant, every interval for an empty ring or a ring of v alone.  It owns
+ * its device buffers (per node up to 100 arcs, and the census' claims(i):
+ * about 79 MB at 65,536 nodes); any number may be live, and a snapshot and its
+ * simulation may be destroyed in either order.
+ * rp_ownership_snapshot_info: the census' stats at the snapshot and its clock
+ * (each may be NULL).
+ *
+ * rp_sim_ownership_moved compares `from` with `to`, or with the simulation as
+ * it is now when `to` is NULL (through the census' cache: without a call that
+ * can change a ring in between, the current arcs are recorded once).  Node v
+ * gains C_to(v) \ C_from(v) and loses C_from(v) \ C_to(v); gained[v] and
+ * lost[v] (each NULL, or cap >= n entries) are the numbers of hashes in them,
+ * 0 to 2^32.  Per interval i, g(i) nodes gain it and l(i) lose it, and
+ * claims_to(i) = claims_from(i) + g(i) - l(i).  In the stats
+ *   transition[a][b]  hashes with min(claims_from, 2) = a and
+ *                     min(claims_to, 2) = b (the nine sum to 2^32);
+ *   same_set          hashes with g = l = 0;
+ *   handed_off        hashes with claims_from = claims_to = 1 and g = l = 1:
+ *                     one owner before, another after;
+ *   gained, lost      the sums of gained[v] and lost[v]; gainers, losers the
+ *                     numbers of nodes where they are not 0;
+ *   max_gained(_node), max_lost(_node)  the largest, and the lowest node id
+ *                     that reaches it (node 0 when nothing moved);
+ *   max_turnover(_hash)  the largest g(i) + l(i) and the pt_hash[i] of the
+ *                     lowest such interval (hash 0 when nothing moved);
+ *   from_clock, to_clock, intervals  the two clocks and the interval count.
+ * Exact, on the device, in time proportional to the ring's points.  Errors:
+ * RP_ERR_UNSUPPORTED on one rank of a multi-process or loop cluster (as for
+ * the census); RP_ERR_INVALID for a snapshot of another simulation or
+ * cap < n; RP_ERR_STATE for a snapshot taken before rp_sim_load_addresses
+ * changed the points. */
+typedef struct rp_ownership_snapshot rp_ownership_snapshot;
+typedef struct {
+    uint64_t transition[3][3];
+    uint64_t same_set, handed_off, gained, lost, gainers, losers;
+    uint64_t max_gained, max_gained_node, max_lost, max_lost_node, max_turnover, max_turnover_hash;
+    uint64_t from_clock, to_clock, intervals;
+    uint64_t reserved[8];
+} rp_movement_stats;
+int rp_ownership_snapshot_create(rp_sim *sim, rp_ownership_snapshot **out);
+int rp_ownership_snapshot_info(const rp_ownership_snapshot *snap, rp_ownership_stats *stats, uint64_t *clock);
+int rp_ownership_snapshot_destroy(rp_ownership_snapshot *snap);
+int rp_sim_ownership_moved(rp_sim *sim, const rp_ownership_snapshot *from, const rp_ownership_snapshot *to,
+                           rp_movement_stats *stats, uint64_t *gained, uint64_t *lost, size_t cap);
+
 /* ---- Request traffic with proxy retries across rounds ------------------------
  * Replaces the RequestProxySend state machine (lib/request-proxy/send.js) for
  * batches of single-key requests that live across rounds: a tracker keeps a

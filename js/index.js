@@ -616,6 +616,30 @@ SimCluster.prototype.ownership = function ownership() { return addon.simOwnershi
 SimCluster.prototype.ownershipAt = function ownershipAt(keyHashes) {
     return addon.simOwnershipAt(this._sim, keyHashes);
 };
+// Ownership movement between two instants (rp_ownership_snapshot_*,
+// rp_sim_ownership_moved).  ownershipSnapshot() fixes every instance's claim
+// set now: {clock, stats, close()}; it owns device memory until closed or
+// collected.  ownershipMoved(from, to) compares two snapshots, or `from` with
+// the cluster as it is now when `to` is omitted: {transition: [3][3],
+// sameSet, handedOff, gained, lost, gainers, losers, maxGained, maxGainedNode,
+// maxLost, maxLostNode, maxTurnover, maxTurnoverHash, fromClock, toClock,
+// intervals, gainedBy, lostBy: BigUint64Arrays of the hashes each instance
+// gained and lost}
+function OwnershipSnapshot(cluster) {
+    var r = addon.simOwnershipSnapshot(cluster._sim);
+    this._h = r.handle;
+    this.clock = r.clock;
+    this.stats = r.stats;
+}
+OwnershipSnapshot.prototype.close = function close() { addon.simOwnershipSnapshotClose(this._h); };
+SimCluster.OwnershipSnapshot = OwnershipSnapshot;
+SimCluster.prototype.ownershipSnapshot = function ownershipSnapshot() { return new OwnershipSnapshot(this); };
+SimCluster.prototype.ownershipMoved = function ownershipMoved(from, to) {
+    if (!(from instanceof OwnershipSnapshot) || (to != null && !(to instanceof OwnershipSnapshot))) {
+        throw new TypeError('ownershipMoved: from must be an ownership snapshot, to one or omitted');
+    }
+    return addon.simOwnershipMoved(this._sim, from._h, to ? to._h : null);
+};
 // Request traffic with the request proxy's retries across rounds
 // (rp_traffic_*; lib/request-proxy/send.js): opts {maxRetries: 3, schedule:
 // [0, 5, 18] rounds, enforceConsistency: true, track: false, capacity: 2^20}.

@@ -664,6 +664,126 @@ static napi_value js_sim_ownership_at(napi_env env, napi_callback_info info) {
     return ta;
 }
 
+/* ---- ownership movement (rp_ownership_snapshot_*, rp_sim_ownership_moved): a
+ * snapshot owns its device buffers and needs no simulation to be freed */
+typedef struct {
+    rp_ownership_snapshot *s;
+} snapshot_handle;
+
+static void snapshot_finalize(napi_env env, void *data, void *hint) {
+    (void)env; (void)hint;
+    snapshot_handle *h = (snapshot_handle *)data;
+    if (h->s) rp_ownership_snapshot_destroy(h->s);
+    free(h);
+}
+
+/* simOwnershipSnapshot(sim) -> {handle, clock, stats: simOwnership's fields without claimed} */
+static napi_value js_sim_ownership_snapshot(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1], ext, o, so, m;
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    snapshot_handle *h = (snapshot_handle *)calloc(1, sizeof *h);
+    if (!h) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+    int rc = rp_ownership_snapshot_create((rp_sim *)get_external(env, argv[0]), &h->s);
+    if (rc != RP_OK) { free(h); return throw_rp(env, rc); }
+    rp_ownership_stats st;
+    uint64_t clock = 0;
+    memset(&st, 0, sizeof st);
+    rp_ownership_snapshot_info(h->s, &st, &clock);
+    if (napi_create_external(env, h, snapshot_finalize, NULL, &ext) != napi_ok) {
+        rp_ownership_snapshot_destroy(h->s);
+        free(h);
+        napi_throw_error(env, NULL, "N-API call failed");
+        return NULL;
+    }
+    napi_create_array_with_length(env, 8, &m);
+    for (uint32_t k = 0; k < 8; k++) napi_set_element(env, m, k, num(env, (double)st.measure[k]));
+    napi_create_object(env, &so);
+    napi_set_named_property(env, so, "measure", m);
+    napi_set_named_property(env, so, "claimants", num(env, (double)st.claimants));
+    napi_set_named_property(env, so, "intervals", num(env, (double)st.intervals));
+    napi_set_named_property(env, so, "maxClaims", num(env, (double)st.max_claims));
+    napi_set_named_property(env, so, "maxClaimsHash", num(env, (double)st.max_claims_hash));
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "handle", ext);
+    napi_set_named_property(env, o, "clock", num(env, (double)clock));
+    napi_set_named_property(env, o, "stats", so);
+    return o;
+}
+
+static napi_value js_sim_ownership_snapshot_close(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1];
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    snapshot_handle *h = (snapshot_handle *)get_external(env, argv[0]);
+    if (h && h->s) {
+        rp_ownership_snapshot_destroy(h->s);
+        h->s = NULL;
+    }
+    return NULL;
+}
+
+/* simOwnershipMoved(sim, from, to | null) -> {transition: [3][3], sameSet, handedOff, gained, lost,
+ * gainers, losers, maxGained, maxGainedNode, maxLost, maxLostNode, maxTurnover, maxTurnoverHash,
+ * fromClock, toClock, intervals, gainedBy, lostBy: BigUint64Array} (rp_sim_ownership_moved; every
+ * number is at most 2^33: exact as a double) */
+static napi_value js_sim_ownership_moved(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3], o, t, row;
+    CHECK_NAPI(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    rp_sim *sim;
+    uint32_t n;
+    CHECK_RP(sim_size(env, argv[0], &sim, &n));
+    const rp_ownership_snapshot *snap[2] = {NULL, NULL};
+    for (size_t k = 1; k < 3; k++) {
+        napi_valuetype vt = napi_undefined;
+        if (k < argc) napi_typeof(env, argv[k], &vt);
+        if (vt == napi_external) {
+            snapshot_handle *h = (snapshot_handle *)get_external(env, argv[k]);
+            if (!h || !h->s) {
+                napi_throw_error(env, NULL, "ownership snapshot is closed");
+                return NULL;
+            }
+            snap[k - 1] = h->s;
+        } else if (k == 1 || (vt != napi_undefined && vt != napi_null)) {
+            napi_throw_type_error(env, NULL, "from must be an ownership snapshot, to one or null");
+            return NULL;
+        }
+    }
+    void *g, *l;
+    napi_value ga = typed(env, napi_biguint64_array, (size_t)n, 8, &g);
+    napi_value la = typed(env, napi_biguint64_array, (size_t)n, 8, &l);
+    rp_movement_stats st;
+    memset(&st, 0, sizeof st);
+    CHECK_RP(rp_sim_ownership_moved(sim, snap[0], snap[1], &st, (uint64_t *)g, (uint64_t *)l, n));
+    napi_create_array_with_length(env, 3, &t);
+    for (uint32_t a = 0; a < 3; a++) {
+        napi_create_array_with_length(env, 3, &row);
+        for (uint32_t b = 0; b < 3; b++) napi_set_element(env, row, b, num(env, (double)st.transition[a][b]));
+        napi_set_element(env, t, a, row);
+    }
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "transition", t);
+    napi_set_named_property(env, o, "sameSet", num(env, (double)st.same_set));
+    napi_set_named_property(env, o, "handedOff", num(env, (double)st.handed_off));
+    napi_set_named_property(env, o, "gained", num(env, (double)st.gained));
+    napi_set_named_property(env, o, "lost", num(env, (double)st.lost));
+    napi_set_named_property(env, o, "gainers", num(env, (double)st.gainers));
+    napi_set_named_property(env, o, "losers", num(env, (double)st.losers));
+    napi_set_named_property(env, o, "maxGained", num(env, (double)st.max_gained));
+    napi_set_named_property(env, o, "maxGainedNode", num(env, (double)st.max_gained_node));
+    napi_set_named_property(env, o, "maxLost", num(env, (double)st.max_lost));
+    napi_set_named_property(env, o, "maxLostNode", num(env, (double)st.max_lost_node));
+    napi_set_named_property(env, o, "maxTurnover", num(env, (double)st.max_turnover));
+    napi_set_named_property(env, o, "maxTurnoverHash", num(env, (double)st.max_turnover_hash));
+    napi_set_named_property(env, o, "fromClock", num(env, (double)st.from_clock));
+    napi_set_named_property(env, o, "toClock", num(env, (double)st.to_clock));
+    napi_set_named_property(env, o, "intervals", num(env, (double)st.intervals));
+    napi_set_named_property(env, o, "gainedBy", ga);
+    napi_set_named_property(env, o, "lostBy", la);
+    return o;
+}
+
 /* ---- request traffic with proxy retries (rp_traffic_*): a tracker handle keeps
  * its simulation's handle alive until it is closed or collected */
 typedef struct {
@@ -1609,6 +1729,9 @@ static napi_value init(napi_env env, napi_value exports) {
     EXPORT("simRoute", js_sim_route);
     EXPORT("simOwnership", js_sim_ownership);
     EXPORT("simOwnershipAt", js_sim_ownership_at);
+    EXPORT("simOwnershipSnapshot", js_sim_ownership_snapshot);
+    EXPORT("simOwnershipSnapshotClose", js_sim_ownership_snapshot_close);
+    EXPORT("simOwnershipMoved", js_sim_ownership_moved);
     EXPORT("trafficCreate", js_traffic_create);
     EXPORT("trafficClose", js_traffic_close);
     EXPORT("trafficSubmit", js_traffic_submit);

@@ -58,6 +58,20 @@ class OwnershipStats(ctypes.Structure):
         return d
 
 
+MOVEMENT_SCALARS = ("same_set", "handed_off", "gained", "lost", "gainers", "losers", "max_gained", "max_gained_node",
+                    "max_lost", "max_lost_node", "max_turnover", "max_turnover_hash", "from_clock", "to_clock", "intervals")
+
+
+class MovementStats(ctypes.Structure):
+    _fields_ = ([("transition", ctypes.c_uint64 * 3 * 3)] + [(k, ctypes.c_uint64) for k in MOVEMENT_SCALARS] +
+                [("reserved", ctypes.c_uint64 * 8)])
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in MOVEMENT_SCALARS}
+        d["transition"] = [[int(x) for x in row] for row in self.transition]
+        return d
+
+
 class TrafficConfig(ctypes.Structure):
     _fields_ = [("max_retries", ctypes.c_int32), ("nschedule", ctypes.c_uint32), ("schedule", ctypes.c_uint32 * 8),
                 ("enforce_consistency", ctypes.c_int32), ("track", ctypes.c_uint32), ("timing", ctypes.c_uint32),
@@ -178,6 +192,10 @@ SIGNATURES = {
     "rp_sim_route_uniform": ([_P, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(RouteStats)], ctypes.c_int),
     "rp_sim_ownership": ([_P, ctypes.POINTER(OwnershipStats), _P, _SZ], ctypes.c_int),
     "rp_sim_ownership_at": ([_P, _P, _SZ, _P], ctypes.c_int),
+    "rp_ownership_snapshot_create": ([_P, ctypes.POINTER(_P)], ctypes.c_int),
+    "rp_ownership_snapshot_info": ([_P, ctypes.POINTER(OwnershipStats), _U64P], ctypes.c_int),
+    "rp_ownership_snapshot_destroy": ([_P], ctypes.c_int),
+    "rp_sim_ownership_moved": ([_P, _P, _P, ctypes.POINTER(MovementStats), _P, _P, _SZ], ctypes.c_int),
     "rp_traffic_create": ([_P, ctypes.POINTER(TrafficConfig), ctypes.POINTER(_P)], ctypes.c_int),
     "rp_traffic_destroy": ([_P], ctypes.c_int),
     "rp_traffic_submit": ([_P, _P, _P, _SZ, _U64P], ctypes.c_int),

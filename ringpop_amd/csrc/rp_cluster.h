@@ -377,7 +377,20 @@ struct rp_sim {
     rp::DevBuf<const uint8_t*> own_dead;
     rp_ownership_stats own_stats{};
     rp::OwnArgs own_args();
-    void own_refresh();
+    void own_prepare();
+    void own_refresh(bool record = false);
+    // ownership movement (rp_ownership_snapshot_* / rp_sim_ownership_moved;
+    // DESIGN.md §15).  A census run for a snapshot or a comparison also
+    // records every node's arcs (own_arcs_valid: they are the cached census');
+    // the plain census never does.  own_id names this simulation in its
+    // snapshots (given at the first one); own_gen counts the builds of the
+    // server -> point index, so that a snapshot of other points is refused.
+    bool own_arcs_valid = false;
+    uint64_t own_id = 0, own_gen = 0;
+    rp::DevBuf<uint32_t> own_arc_n;  // n: arcs recorded, or OWN_ARC_ALL
+    rp::DevBuf<uint2> own_arcs;      // n x REPLICAS: (q, p) by ascending p
+    rp::DevBuf<int32_t> mv_diff, mv_tile;
+    rp::DevBuf<unsigned long long> mv_gained, mv_lost, mv_out;
     template <bool UNIFORM>
     void route_launch(const uint32_t* entries, const uint32_t* keys, uint64_t seed, uint64_t count, int32_t* dests,
                       uint8_t* outcomes, uint8_t* agrees, rp_route_stats* stats);

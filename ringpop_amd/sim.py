@@ -3,7 +3,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (OwnershipStats, RequestPending, RequestResult, RoundStats, RouteStats, SimConfig, TrafficConfig, TrafficStats, check,
+from ._lib import (MovementStats, OwnershipStats, RequestPending, RequestResult, RoundStats, RouteStats, SimConfig, TrafficConfig, TrafficStats, check,
                    lib, ptr)
 
 KERNEL_CATEGORIES = ("churn", "issue", "merge_ping", "merge_resp", "checksum", "other")
@@ -125,6 +125,39 @@ class Traffic:
         check(lib().rp_traffic_times(self._h, ms, calls, ctypes.byref(peak)))
         return {"poll_ms": ms[0], "polls": int(calls[0]), "submit_ms": ms[1], "submits": int(calls[1]),
                 "peak_pending": int(peak.value)}
+
+
+class OwnershipSnapshot:
+    """rp_ownership_snapshot: every node's claim set at one clock
+    (Sim.ownership_snapshot).  `clock` is the round count it
+    was taken at, `stats` the census' stats dict then.  It owns its device
+    buffers: close it (or use it as a context manager) when done; it may
+    outlive its Sim."""
+
+    def __init__(self, sim):
+        self._h = ctypes.c_void_p()
+        check(lib().rp_ownership_snapshot_create(sim._h, ctypes.byref(self._h)))
+        st, clock = OwnershipStats(), ctypes.c_uint64(0)
+        check(lib().rp_ownership_snapshot_info(self._h, ctypes.byref(st), ctypes.byref(clock)))
+        self.stats = st.as_dict()
+        self.clock = int(clock.value)
+
+    def close(self):
+        if self._h:
+            lib().rp_ownership_snapshot_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Sim:
@@ -414,6 +447,28 @@ class Sim:
         out = np.zeros(len(h), dtype=np.uint32)
         check(lib().rp_sim_ownership_at(self._h, ptr(h), len(h), ptr(out)))
         return out
+
+    # ---- ownership movement between two instants (rp_sim_ownership_moved)
+    def ownership_snapshot(self):
+        """Every node's claim set now, to compare later (an OwnershipSnapshot)."""
+        return OwnershipSnapshot(self)
+
+    def ownership_moved(self, frm, to=None):
+        """Which keys changed hands between snapshot `frm` and snapshot `to`
+        (None: the simulation as it is now): a dict of rp_movement_stats'
+        fields (`transition` as 3 x 3 lists) plus `gained_by` and `lost_by`
+        (the JS host's gainedBy / lostBy): per node the hashes it claims at
+        `to` and not at `frm`, and the reverse, as uint64 arrays whose sums
+        are the stats' `gained` and `lost`."""
+        st = MovementStats()
+        gained = np.zeros(self.n, dtype=np.uint64)
+        lost = np.zeros(self.n, dtype=np.uint64)
+        check(lib().rp_sim_ownership_moved(self._h, frm._h, to._h if to is not None else None, ctypes.byref(st),
+                                           ptr(gained), ptr(lost), self.n))
+        d = st.as_dict()
+        d["gained_by"] = gained
+        d["lost_by"] = lost
+        return d
 
     def traffic(self, **cfg):
         """A request tracker on this simulation (rp_traffic_create): max_retries=3,
