@@ -293,6 +293,53 @@ if (want('ring')) {
     write('ring_collisions.json', { replica_points: R, table: table, probes: probes, steps: steps });
 }
 
+// ---------------------------------------------------------------- ring edges
+// The hashFunc seam again, with the points at the ends of the hash space:
+// 6 servers x 4 replicas whose table holds 0, 4294967295 and hashes several
+// servers share; D's hashes are all taken while A and B are present, so it is
+// a present server that owns nothing.  Probes at p, p - 1, p + 1 of every
+// table value.  After each step the rbtree, lookup and lookupN for
+// n in {0, 1, 2, 3, 5} (n = 0: the do-while of lib/ring.js:150-182 still
+// returns one owner unless the key lies past the largest point).
+if (want('ring_edges')) {
+    var EdgeRing = require(path.join(REF, 'lib/ring.js'));
+    var etable = {
+        A: [0, 1000, 2000, 4294967295], B: [1000, 3000, 3001, 5000], C: [2999, 3002, 7000, 4294967294],
+        D: [0, 1000, 3000, 4294967295], E: [1, 5000, 7000, 9000], F: [2000, 2147483648, 2147483647, 65536]
+    };
+    var ehash = {};
+    var evals = {};
+    Object.keys(etable).forEach(function (sv) {
+        etable[sv].forEach(function (h, i) {
+            ehash[sv + i] = h;
+            [h - 1, h, h + 1].forEach(function (p) { if (p >= 0 && p <= 4294967295) evals[p] = true; });
+        });
+    });
+    var eprobes = Object.keys(evals).map(Number).sort(function (a, b) { return a - b; });
+    var ehf = function (str) { return ehash[str] !== undefined ? ehash[str] : Number(str.slice(4)); };
+    var eops = [
+        [['A', 'B', 'C', 'D'], []], [[], ['A']], [['E', 'F'], []], [['A'], ['D']], [[], ['B', 'C', 'E']],
+        [['D'], ['F']], [[], ['A', 'D']]
+    ];
+    var ering = new EdgeRing({ hashFunc: ehf, replicaPoints: 4 });
+    var ens = [0, 1, 2, 3, 5];
+    var esteps = eops.map(function (op) {
+        var changed = ering.addRemoveServers(op[0], op[1]);
+        var pts = [];
+        var it = ering.rbtree.iterator();
+        for (var v = it.next(); v !== null; v = it.next()) pts.push([v, it.str()]);
+        var byN = {};
+        ens.forEach(function (n) {
+            byN[n] = eprobes.map(function (p) { return ering.lookupN('key:' + p, n); });
+        });
+        return { add: op[0], remove: op[1], changed: changed, points: pts,
+            servers: Object.keys(ering.servers).sort(), server_count: ering.getServerCount(),
+            lookups: eprobes.map(function (p) { var o = ering.lookup('key:' + p); return o === undefined ? null : o; }),
+            lookupN: byN };
+    });
+    write('ring_edges.json', { replica_points: 4, table: etable, probes: eprobes, ns: ens, steps: esteps });
+}
+
 // ---------------------------------------------------------------- piggyback
 if (want('piggyback')) {
     var Dissemination = require(path.join(REF, 'lib/dissemination.js'));

@@ -251,10 +251,12 @@ __global__ void __launch_bounds__(256) k_dir_both(const uint32_t* h, const int32
     const uint32_t base = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
     if ((b & ((1u << D16_GROUP_LOG) - 1u)) == 0) coarse[b >> D16_GROUP_LOG] = lo;
     uint32_t e;
+    bool esc = false;
     if (lo == n) e = (uint32_t)own[0];
     else if (hv >= last) e = (uint32_t)own[lo];
-    else e = 0x8000u | (lo - base);
-    if ((e & 0x8000u) ? (lo - base) >= 0x8000u : e >= 0x8000u) atomicOr(bad, 1u);
+    else { e = 0x8000u | (lo - base); esc = true; }
+    // (by the branch taken, not by bit 15 of e: an owner id >= 0x8000 is not an escape)
+    if (esc ? (lo - base) >= 0x8000u : e >= 0x8000u) atomicOr(bad, 1u);
     dir16[b] = (uint16_t)e;
 }
 

@@ -6,8 +6,10 @@ merge thread, one ping rank before k_phase2, the per-lane checksum render,
 no checksum side stream, cross-shard seen masks per 2 nodes, compaction at
 2x + 1,024, the ring's 32-bit directory only and every ring update through
 the bulk path.  None of them changes a result, so the reference fixtures,
-the oracle comparisons and the ring's per-call checks must hold as they do
-for the defaults (only the defaults were under the oracle).
+the oracle comparisons, the ring's per-call checks and its placed-point
+scenarios (test_gpu_ring_edges.py: here every call through the bulk sort and
+every lookup through the 32-bit directory) must hold as they do for the
+defaults (only the defaults were under the oracle).
 The library is loaded in a child pytest (RINGPOP_HIP_LIB), one process."""
 import os
 import subprocess
@@ -26,11 +28,12 @@ def test_alt_constants_parity():
     env = dict(os.environ, RINGPOP_HIP_LIB=lib)
     cmd = [sys.executable, "-u", "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider", "-m", "gpu",
            "--timeout", "240", "--timeout-method", "thread",
-           "tests/test_gpu_parity.py", "tests/test_gpu_ring_incremental.py",
+           "tests/test_gpu_parity.py", "tests/test_gpu_ring_incremental.py", "tests/test_gpu_ring_edges.py",
            "-k", "sim_small or storm or lane_per_view or n256 or medium or ring or farmhash"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)
     tail = (r.stdout[-4000:] + "\n" + r.stderr[-2000:])
     assert r.returncode == 0, tail
     import re
     m = re.search(r"(\d+) passed", r.stdout)
-    assert m and int(m.group(1)) >= 30 and "failed" not in r.stdout, tail  # (the selection ran: ~50 tests)
+    # (the selection ran: ~50 tests and the 23 of test_gpu_ring_edges.py, which "ring" selects by its file name)
+    assert m and int(m.group(1)) >= 53 and "failed" not in r.stdout, tail
