@@ -521,6 +521,65 @@ int rp_ownership_snapshot_destroy(rp_ownership_snapshot *snap);
 int rp_sim_ownership_moved(rp_sim *sim, const rp_ownership_snapshot *from, const rp_ownership_snapshot *to,
                            rp_movement_stats *stats, uint64_t *gained, uint64_t *lost, size_t cap);
 
+/* ---- Replica-set census (between rounds) --------------------------------------
+ * What a service that replicates through lookupN(key, R) sees:
+ * for the whole 2^32 hash space, how many live nodes believe they hold one of
+ * a key's R replicas.  The clock, the claimants and the intervals are the
+ * ownership census'.  A view's points are the points some server of its ring
+ * owns.  lookupN_v(h, n) (lib/ring.js:150-182) starts from the first such
+ * point >= h, wraps, walks the view's points once round and keeps each owner
+ * the first time it appears, until n are kept.  Claimant v holds h at R iff v
+ * is in lookupN_v(h, R), or v's ring is empty (RingPop.lookupN returns
+ * [whoami], index.js:438-443).  claims_R(i) is the number of claimants that
+ * hold interval i.
+ *
+ * rp_sim_ring_lookup_n: HashRing.lookupN in one node's view, for precomputed
+ * key hashes: out is [nkeys * n] with unused slots -1, counts[k] the owners
+ * found (<= min(n, servers of that ring); 0 on an empty ring: the whoami
+ * fallback is RingPop.lookupN's, and is the census' rule above).  n is in
+ * [0, 16].
+ *
+ * rp_sim_replication, replicas R in [1, 8]: measure[k] is the number of
+ * hashes that exactly k nodes believe they hold (k < 15; measure[15]: 15 or
+ * more; the sixteen sum to 2^32); under / exact / over the hashes with fewer
+ * than, exactly and more than R such nodes (they sum to 2^32); max_claims and
+ * min_claims the largest and smallest claims_R(i), each with the pt_hash[i]
+ * of the lowest interval that reaches it; arcs the arcs the views contributed
+ * and walk_steps the steps their walks took (a diagnostic of the work done,
+ * not of the cluster: DESIGN.md §16).  held (NULL, or cap >= n entries)
+ * gets per node the number of hashes it holds: 0 for a node that is no
+ * claimant, 2^32 for an empty ring and for a node that owns a point in a ring
+ * of at most R servers.  With R = 1 every field shared with rp_ownership_stats,
+ * held against claimed, and rp_sim_replication_at against rp_sim_ownership_at
+ * equal the ownership census'.
+ *
+ * rp_sim_replication_at: claims[j] = claims_R(i) of the interval
+ * key_hashes[j] falls in; it computes the census for R unless that is the
+ * cached one.
+ *
+ * Exact, on the device, in time proportional to the ring's points, and cached
+ * like the ownership census with the R the result was computed for: a second
+ * call with the same R and no call that can change a ring in between only
+ * copies, another R recomputes.  All three need every node's view on this
+ * process's device: RP_ERR_UNSUPPORTED on one rank of a multi-process or loop
+ * cluster; in-process shards give the one-shard results.  RP_ERR_INVALID for
+ * R outside [1, 8], n outside [0, 16], a bad node id, or a held buffer with
+ * cap < n (before any state changes). */
+int rp_sim_ring_lookup_n(rp_sim *sim, uint32_t node, const uint32_t *key_hashes, size_t nkeys, int n,
+                         int32_t *out, int32_t *counts);
+typedef struct {
+    uint64_t measure[16];
+    uint64_t replicas;
+    uint64_t claimants, intervals;
+    uint64_t under, exact, over;
+    uint64_t max_claims, max_claims_hash;
+    uint64_t min_claims, min_claims_hash;
+    uint64_t walk_steps, arcs;
+    uint64_t reserved[4];
+} rp_replication_stats;
+int rp_sim_replication(rp_sim *sim, uint32_t replicas, rp_replication_stats *stats, uint64_t *held, size_t cap);
+int rp_sim_replication_at(rp_sim *sim, uint32_t replicas, const uint32_t *key_hashes, size_t n, uint32_t *claims);
+
 /* ---- Request traffic with proxy retries across rounds ------------------------
  * Replaces the RequestProxySend state machine (lib/request-proxy/send.js) for
  * batches of single-key requests that live across rounds: a tracker keeps a

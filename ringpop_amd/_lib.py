@@ -58,6 +58,20 @@ class OwnershipStats(ctypes.Structure):
         return d
 
 
+REPLICATION_SCALARS = ("replicas", "claimants", "intervals", "under", "exact", "over", "max_claims", "max_claims_hash",
+                       "min_claims", "min_claims_hash", "walk_steps", "arcs")
+
+
+class ReplicationStats(ctypes.Structure):
+    _fields_ = ([("measure", ctypes.c_uint64 * 16)] + [(k, ctypes.c_uint64) for k in REPLICATION_SCALARS] +
+                [("reserved", ctypes.c_uint64 * 4)])
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in REPLICATION_SCALARS}
+        d["measure"] = [int(x) for x in self.measure]
+        return d
+
+
 MOVEMENT_SCALARS = ("same_set", "handed_off", "gained", "lost", "gainers", "losers", "max_gained", "max_gained_node",
                     "max_lost", "max_lost_node", "max_turnover", "max_turnover_hash", "from_clock", "to_clock", "intervals")
 
@@ -192,6 +206,9 @@ SIGNATURES = {
     "rp_sim_route_uniform": ([_P, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(RouteStats)], ctypes.c_int),
     "rp_sim_ownership": ([_P, ctypes.POINTER(OwnershipStats), _P, _SZ], ctypes.c_int),
     "rp_sim_ownership_at": ([_P, _P, _SZ, _P], ctypes.c_int),
+    "rp_sim_ring_lookup_n": ([_P, ctypes.c_uint32, _P, _SZ, ctypes.c_int, _P, _P], ctypes.c_int),
+    "rp_sim_replication": ([_P, ctypes.c_uint32, ctypes.POINTER(ReplicationStats), _P, _SZ], ctypes.c_int),
+    "rp_sim_replication_at": ([_P, ctypes.c_uint32, _P, _SZ, _P], ctypes.c_int),
     "rp_ownership_snapshot_create": ([_P, ctypes.POINTER(_P)], ctypes.c_int),
     "rp_ownership_snapshot_info": ([_P, ctypes.POINTER(OwnershipStats), _U64P], ctypes.c_int),
     "rp_ownership_snapshot_destroy": ([_P], ctypes.c_int),

@@ -4,7 +4,7 @@
 // (rp_sim).  Member functions that launch a round kernel are declared here and
 // defined beside the kernels in rp_sim.hip; a feature that adds no round
 // kernel lives in a file of its own (rp_route.hip, rp_traffic.hip, rp_own.hip,
-// rp_xport.hip) and reaches the cluster through this header.
+// rp_repl.hip, rp_xport.hip) and reaches the cluster through this header.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,7 +22,7 @@ struct rp_loop;
 
 namespace rp {
 
-struct OwnArgs;  // rp_own.hip
+struct OwnArgs;  // rp_own.h
 
 constexpr int NCAT = 7;  // churn, issue, merge_ping, merge_resp, checksum, other, exchange
 constexpr int CAT_SIDE = NCAT;  // a span of a shard's side stream (Shard::side_ms; no stage of its own)
@@ -355,10 +355,11 @@ struct rp_sim {
     // (rp_sim_load_addresses)
     bool ring_csum_stale = true;
     // an entry point that can change a ring ran: both caches (this one and
-    // the census') are stale
+    // the censuses') are stale
     void rings_changed() {
         ring_csum_stale = true;
         own_stale = true;
+        rep_stale = true;
     }
     rp::DevBuf<rp::RouteShard> route_tab;
     rp::DevBuf<uint32_t> route_dir;
@@ -391,6 +392,18 @@ struct rp_sim {
     rp::DevBuf<uint2> own_arcs;      // n x REPLICAS: (q, p) by ascending p
     rp::DevBuf<int32_t> mv_diff, mv_tile;
     rp::DevBuf<unsigned long long> mv_gained, mv_lost, mv_out;
+    // replica-set census (rp_sim_replication / rp_sim_replication_at;
+    // rp_repl.hip): the census' cache rule with a flag of its
+    // own and the R the cached result holds for (0: none).  Its counts per
+    // interval and per node live in buffers of their own, so that the census'
+    // and the snapshots' are not disturbed; diff and tile sums are scratch.
+    bool rep_stale = true;
+    uint32_t rep_r = 0;
+    rp::DevBuf<uint32_t> rep_claims;
+    rp::DevBuf<int32_t> rep_diff, rep_tile;
+    rp::DevBuf<unsigned long long> rep_held, rep_out;
+    rp_replication_stats rep_stats{};
+    void rep_refresh(uint32_t replicas);
     template <bool UNIFORM>
     void route_launch(const uint32_t* entries, const uint32_t* keys, uint64_t seed, uint64_t count, int32_t* dests,
                       uint8_t* outcomes, uint8_t* agrees, rp_route_stats* stats);

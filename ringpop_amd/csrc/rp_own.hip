@@ -13,7 +13,7 @@
 #include <memory>
 #include <string>
 
-#include "rp_cluster.h"
+#include "rp_own.h"
 
 namespace rp {
 
@@ -21,28 +21,8 @@ namespace rp {
 // count, and the largest claim count packed with its first interval
 // (claims << 32 | ~index, so that an atomic max keeps the lowest index)
 enum : uint32_t { OWN_MEASURE = 0, OWN_CLAIMANTS = 8, OWN_MAX = 9, OWN_NOUT = 10 };
-constexpr uint32_t OWN_REPLICAS = (uint32_t)REPLICAS;
-constexpr uint32_t OWN_BLOCK = 256;     // threads of a scan block ...
-constexpr uint32_t OWN_ITEMS = 8;       // ... and consecutive intervals of each
-constexpr uint32_t OWN_TILE = OWN_BLOCK * OWN_ITEMS;
 constexpr uint32_t OWN_WALK_STEPS = 4;  // backward steps a lane takes alone before the wave searches for it
 constexpr uint32_t OWN_ARC_ALL = 0x80000000u;  // a recorded arc count: the node claims every interval
-
-struct OwnArgs {
-    const RouteShard* tab;            // node v's rows: row v % nl of shard v / nl
-    const uint8_t* const* dead;       // per shard: n bytes by global id (valid for the shard's own nodes)
-    const uint32_t* pt_hash;
-    const int32_t* pt_server;
-    const int32_t* pt_coll;
-    const uint32_t* dir;
-    const uint32_t* srv_pt;           // n x OWN_REPLICAS point indices, each row ascending
-    uint32_t n, nl, ncoll, npts, dir_shift, ntiles;
-    int32_t* diff;                    // npts + 1
-    uint32_t* claims;                 // npts
-    int32_t* tile_sum;                // ntiles: each tile's sum of diff, then its exclusive prefix
-    unsigned long long* claimed;      // n
-    unsigned long long* out;          // OWN_NOUT
-};
 
 // replica hash -> index of its point (every replica hash is a point: the
 // search is exact).  The host sorted each server's hashes, so a row's indices
@@ -51,12 +31,6 @@ __global__ void __launch_bounds__(256) k_own_point_index(OwnArgs A, const uint32
     const uint64_t total = (uint64_t)A.n * OWN_REPLICAS;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x)
         srv_pt[i] = route_point(A.pt_hash, A.npts, A.dir, A.dir_shift, rep_hash[i]);
-}
-
-__device__ inline unsigned long long wave_sum_u64(unsigned long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-    return x;
 }
 
 // One wave per view v.  v claims the arcs that end at its own points in its
@@ -167,15 +141,6 @@ __global__ void __launch_bounds__(OWN_BLOCK) k_own_arcs(OwnArgs A, uint32_t* arc
 }
 
 // ---- claims(i): the inclusive prefix sum of diff, in tiles of OWN_TILE
-
-__device__ inline int32_t wave_scan_incl(int32_t x, uint32_t lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int32_t y = __shfl_up(x, o, 64);
-        if (lane >= (uint32_t)o) x += y;
-    }
-    return x;
-}
 
 // each tile's sum of diff
 __global__ void __launch_bounds__(OWN_BLOCK) k_own_tile_sums(OwnArgs A) {
@@ -524,6 +489,11 @@ __global__ void __launch_bounds__(OWN_BLOCK) k_move_finish(MoveArgs A) {
     if (threadIdx.x == MV_HANDED + 1 && bmax) atomicMax(&A.out[MV_MAXT], bmax);
 }
 
+void own_scan_tiles(const OwnArgs& A, hipStream_t st) {
+    hipLaunchKernelGGL(k_own_tile_sums, dim3(A.ntiles), dim3(OWN_BLOCK), 0, st, A);
+    hipLaunchKernelGGL(k_own_tile_scan, dim3(1), dim3(64), 0, st, A);
+}
+
 static unsigned blocks_for(uint64_t items, unsigned per_block, unsigned cap) {
     const uint64_t g = (items + per_block - 1) / per_block;
     return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
@@ -621,8 +591,7 @@ void rp_sim::own_refresh(bool record) {
         else
             hipLaunchKernelGGL(rp::k_own_arcs<false>, dim3((n + per - 1) / per), dim3(rp::OWN_BLOCK), 0, s0.st, A,
                                (uint32_t*)nullptr, (uint2*)nullptr);
-        hipLaunchKernelGGL(rp::k_own_tile_sums, dim3(ntiles), dim3(rp::OWN_BLOCK), 0, s0.st, A);
-        hipLaunchKernelGGL(rp::k_own_tile_scan, dim3(1), dim3(64), 0, s0.st, A);
+        rp::own_scan_tiles(A, s0.st);
         hipLaunchKernelGGL(rp::k_own_finish, dim3(ntiles), dim3(rp::OWN_BLOCK), 0, s0.st, A);
     });
     RP_HIP(hipGetLastError());

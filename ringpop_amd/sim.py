@@ -3,7 +3,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (MovementStats, OwnershipStats, RequestPending, RequestResult, RoundStats, RouteStats, SimConfig, TrafficConfig, TrafficStats, check,
+from ._lib import (MovementStats, OwnershipStats, ReplicationStats, RequestPending, RequestResult, RoundStats, RouteStats, SimConfig, TrafficConfig, TrafficStats, check,
                    lib, ptr)
 
 KERNEL_CATEGORIES = ("churn", "issue", "merge_ping", "merge_resp", "checksum", "other")
@@ -446,6 +446,42 @@ class Sim:
             raise ValueError("ownership_at: one array of key hashes")
         out = np.zeros(len(h), dtype=np.uint32)
         check(lib().rp_sim_ownership_at(self._h, ptr(h), len(h), ptr(out)))
+        return out
+
+    # ---- replica-set census between rounds (rp_sim_replication)
+    def ring_lookup_n(self, v, hashes, n):
+        """HashRing.lookupN(key, n) in node v's view for precomputed key
+        hashes: (owners int32 [nk, n] in preference order, unused slots -1;
+        counts int32 [nk])."""
+        h = np.ascontiguousarray(hashes, dtype=np.uint32)
+        if h.ndim != 1:
+            raise ValueError("ring_lookup_n: one array of key hashes")
+        out = np.full((len(h), max(int(n), 0)), -1, dtype=np.int32)
+        counts = np.zeros(len(h), dtype=np.int32)
+        check(lib().rp_sim_ring_lookup_n(self._h, v, ptr(h), len(h), int(n), ptr(out), ptr(counts)))
+        return out, counts
+
+    def replication(self, replicas):
+        """How many live nodes believe they hold one of a key's `replicas`
+        replicas (lookupN in their own view), over the whole 2^32 hash space:
+        a dict of rp_replication_stats' fields (`measure`: hashes with exactly
+        0..14 such nodes, [15]: 15 or more; `under`, `exact`, `over` against
+        `replicas`) and `held` (per node the hashes it holds, uint64)."""
+        st = ReplicationStats()
+        held = np.zeros(self.n, dtype=np.uint64)
+        check(lib().rp_sim_replication(self._h, int(replicas), ctypes.byref(st), ptr(held), len(held)))
+        d = st.as_dict()
+        d["held"] = held
+        return d
+
+    def replication_at(self, replicas, hashes):
+        """The number of live nodes that believe they hold a replica of each
+        key hash (rp_sim_replication_at)."""
+        h = np.ascontiguousarray(hashes, dtype=np.uint32)
+        if h.ndim != 1:
+            raise ValueError("replication_at: one array of key hashes")
+        out = np.zeros(len(h), dtype=np.uint32)
+        check(lib().rp_sim_replication_at(self._h, int(replicas), ptr(h), len(h), ptr(out)))
         return out
 
     # ---- ownership movement between two instants (rp_sim_ownership_moved; DESIGN.md §15)
