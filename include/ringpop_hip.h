@@ -580,6 +580,30 @@ typedef struct {
 int rp_sim_replication(rp_sim *sim, uint32_t replicas, rp_replication_stats *stats, uint64_t *held, size_t cap);
 int rp_sim_replication_at(rp_sim *sim, uint32_t replicas, const uint32_t *key_hashes, size_t n, uint32_t *claims);
 
+/* ---- Holders query (between rounds) -------------------------------------------
+ * Who the believers are: for key hash h and R in [1, 8],
+ * holders_R(h) is the set of claimants v that hold h at R in the replica-set
+ * census' sense above -- v is in lookupN_v(h, R) in its own view, or v's ring
+ * is empty.  A fail-stopped or not-yet-joined node is never a holder, and a
+ * claimant whose non-empty ring does not contain itself holds nothing.
+ *
+ * rp_sim_holders_at: counts[k] = |holders_R(key_hashes[k])|, the full number
+ * whatever cap is: rp_sim_replication_at's value, and at R = 1
+ * rp_sim_ownership_at's.  holders is [nkeys * cap]: row k holds the
+ * min(cap, counts[k]) lowest node ids of the set in ascending order, unused
+ * slots -1; holders == NULL or cap == 0 gives the counts only.  The result is
+ * deterministic.
+ *
+ * Exact, on the device, computed from the views directly in time proportional
+ * to nodes x keys: it reads neither census and leaves both caches as they
+ * are.  It needs every node's view on this process's device:
+ * RP_ERR_UNSUPPORTED on one rank of a multi-process or loop cluster;
+ * in-process shards give the one-shard result.  RP_ERR_INVALID for R outside
+ * [1, 8], a null sim, or null key_hashes or counts with nkeys > 0 (before any
+ * state changes); nkeys == 0 does nothing. */
+int rp_sim_holders_at(rp_sim *sim, uint32_t replicas, const uint32_t *key_hashes, size_t nkeys, size_t cap,
+                      int32_t *holders, uint32_t *counts);
+
 /* ---- Request traffic with proxy retries across rounds ------------------------
  * Replaces the RequestProxySend state machine (lib/request-proxy/send.js) for
  * batches of single-key requests that live across rounds: a tracker keeps a

@@ -209,6 +209,7 @@ SIGNATURES = {
     "rp_sim_ring_lookup_n": ([_P, ctypes.c_uint32, _P, _SZ, ctypes.c_int, _P, _P], ctypes.c_int),
     "rp_sim_replication": ([_P, ctypes.c_uint32, ctypes.POINTER(ReplicationStats), _P, _SZ], ctypes.c_int),
     "rp_sim_replication_at": ([_P, ctypes.c_uint32, _P, _SZ, _P], ctypes.c_int),
+    "rp_sim_holders_at": ([_P, ctypes.c_uint32, _P, _SZ, _SZ, _P, _P], ctypes.c_int),
     "rp_ownership_snapshot_create": ([_P, ctypes.POINTER(_P)], ctypes.c_int),
     "rp_ownership_snapshot_info": ([_P, ctypes.POINTER(OwnershipStats), _U64P], ctypes.c_int),
     "rp_ownership_snapshot_destroy": ([_P], ctypes.c_int),

@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libringpop_hip.so")
 SOURCES = ["rp_capi.hip", "rp_ring.hip", "rp_sim.hip", "rp_route.hip", "rp_traffic.hip", "rp_own.hip", "rp_repl.hip", "rp_xport.hip",
-           "rp_node.hip", "rp_calib.hip"]
+           "rp_node.hip", "rp_calib.hip", "rp_hold.hip"]
 _INCLUDE_RE = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)
 
 

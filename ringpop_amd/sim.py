@@ -484,6 +484,22 @@ class Sim:
         check(lib().rp_sim_replication_at(self._h, int(replicas), ptr(h), len(h), ptr(out)))
         return out
 
+    # ---- holders query between rounds (rp_sim_holders_at)
+    def holders_at(self, replicas, hashes, cap=16):
+        """Which live nodes believe they hold one of each key hash's
+        `replicas` replicas (lookupN in their own view): (holders int32
+        [nk, cap], per key the lowest node ids in ascending order, unused slots
+        -1; counts uint32 [nk], the full number of holders whatever `cap`:
+        replication_at's value)."""
+        h = np.ascontiguousarray(hashes, dtype=np.uint32)
+        if h.ndim != 1 or int(cap) < 0:
+            raise ValueError("holders_at: one array of key hashes and a row length >= 0")
+        out = np.full((len(h), int(cap)), -1, dtype=np.int32)
+        counts = np.zeros(len(h), dtype=np.uint32)
+        check(lib().rp_sim_holders_at(self._h, int(replicas), ptr(h), len(h), int(cap), ptr(out) if out.size else None,
+                                      ptr(counts)))
+        return out, counts
+
     # ---- ownership movement between two instants (rp_sim_ownership_moved; DESIGN.md §15)
     def ownership_snapshot(self):
         """Every node's claim set now, to compare later (an OwnershipSnapshot)."""
