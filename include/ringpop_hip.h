@@ -604,6 +604,57 @@ int rp_sim_replication_at(rp_sim *sim, uint32_t replicas, const uint32_t *key_ha
 int rp_sim_holders_at(rp_sim *sim, uint32_t replicas, const uint32_t *key_hashes, size_t nkeys, size_t cap,
                       int32_t *holders, uint32_t *counts);
 
+/* ---- Replicated requests (between rounds) --------------------------------------
+ * rp_sim_route_n: what a service that sends a request for a key to all of its
+ * R replicas sees.  Request i enters the cluster at node
+ * e = entries[i] with farmhash32(key) = h = key_hashes[i]; e sends it to every
+ * owner of L = RingPop.lookupN(h, R) in its own view (index.js:429-446), and
+ * each send is judged as rp_sim_route judges its one -- the same clock, the
+ * same liveness, partition window and ring checksums -- and by the holders
+ * query's rule in the destination's own view.  R is in [1, 8]; dests, outcomes
+ * and holds are [n * R], row i slot j at i * R + j, acks is [n].
+ *   e fail-stopped or not yet joined: slot 0 has outcome 4 ENTRY_DEAD, every
+ *     dest is -1, every other slot's outcome is 255, holds and acks are 0.
+ *   Otherwise L is the row rp_sim_ring_lookup_n(e, h, R) returns, with c
+ *     owners; an empty row (an empty ring, or one whose servers own no point)
+ *     stands for L = [e], c = 1.  Slot j < c with d = L[j] takes the first
+ *     rule that applies:
+ *       0 LOCAL             d == e; holds = 1
+ *       3 UNREACHABLE       d is fail-stopped or the partition separates the
+ *                           two; holds = 0
+ *       2 CHECKSUMS_DIFFER  the two nodes' ring checksums differ
+ *       1 DELIVERED         otherwise
+ *     and for outcomes 1 and 2 holds = 1 iff d is in lookupN(h, R) in d's own
+ *     view or d's ring is empty: iff d is in rp_sim_holders_at(R, h)'s set.
+ *   Slots j >= c: dest -1, outcome 255, holds 0.
+ *   acks[i] is the number of slots with outcome 0, 1 or 2 and holds = 1.
+ * The statistics count requests, dead entries, slots (the sum of c), the four
+ * slot outcomes per slot, `misplaced` (slots with outcome 1 or 2 and holds =
+ * 0), `short_lists` (live entries with c < R), acks_hist[k] (live entries with
+ * acks = k) and strict_hist[k] (the same count with CHECKSUMS_DIFFER slots
+ * left out: the request proxy rejects those by default); each histogram sums
+ * to requests - entry_dead.  Every output pointer may be NULL.
+ *
+ * rp_sim_route_n_uniform: the same for `count` requests drawn on the device
+ * by rp_sim_route_uniform's generator, only the statistics returned.
+ *
+ * Exact, on the device, one launch per 2^31 requests; neither census is read
+ * or touched.  Both need every node's view on this process's device:
+ * RP_ERR_UNSUPPORTED on one rank of a multi-process or loop cluster;
+ * in-process shards give the one-shard result.  RP_ERR_INVALID for R outside
+ * [1, 8], a null sim, null entries or key_hashes with n > 0, or an entry >= the
+ * cluster's size (before any state changes); n == 0 does nothing. */
+typedef struct {
+    uint64_t requests, entry_dead, slots;
+    uint64_t local, delivered, checksums_differ, unreachable;
+    uint64_t misplaced, short_lists;
+    uint64_t acks_hist[9], strict_hist[9];
+    uint64_t reserved[5];
+} rp_route_n_stats;
+int rp_sim_route_n(rp_sim *sim, uint32_t replicas, const uint32_t *entries, const uint32_t *key_hashes, size_t n,
+                   int32_t *dests, uint8_t *outcomes, uint8_t *holds, uint8_t *acks, rp_route_n_stats *stats);
+int rp_sim_route_n_uniform(rp_sim *sim, uint32_t replicas, uint64_t seed, uint64_t count, rp_route_n_stats *stats);
+
 /* ---- Request traffic with proxy retries across rounds ------------------------
  * Replaces the RequestProxySend state machine (lib/request-proxy/send.js) for
  * batches of single-key requests that live across rounds: a tracker keeps a

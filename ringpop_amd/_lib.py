@@ -72,6 +72,21 @@ class ReplicationStats(ctypes.Structure):
         return d
 
 
+ROUTE_N_SCALARS = ("requests", "entry_dead", "slots", "local", "delivered", "checksums_differ", "unreachable", "misplaced",
+                   "short_lists")
+
+
+class RouteNStats(ctypes.Structure):
+    _fields_ = ([(k, ctypes.c_uint64) for k in ROUTE_N_SCALARS] +
+                [("acks_hist", ctypes.c_uint64 * 9), ("strict_hist", ctypes.c_uint64 * 9), ("reserved", ctypes.c_uint64 * 5)])
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in ROUTE_N_SCALARS}
+        d["acks_hist"] = [int(x) for x in self.acks_hist]
+        d["strict_hist"] = [int(x) for x in self.strict_hist]
+        return d
+
+
 MOVEMENT_SCALARS = ("same_set", "handed_off", "gained", "lost", "gainers", "losers", "max_gained", "max_gained_node",
                     "max_lost", "max_lost_node", "max_turnover", "max_turnover_hash", "from_clock", "to_clock", "intervals")
 
@@ -210,6 +225,9 @@ SIGNATURES = {
     "rp_sim_replication": ([_P, ctypes.c_uint32, ctypes.POINTER(ReplicationStats), _P, _SZ], ctypes.c_int),
     "rp_sim_replication_at": ([_P, ctypes.c_uint32, _P, _SZ, _P], ctypes.c_int),
     "rp_sim_holders_at": ([_P, ctypes.c_uint32, _P, _SZ, _SZ, _P, _P], ctypes.c_int),
+    "rp_sim_route_n": ([_P, ctypes.c_uint32, _P, _P, _SZ, _P, _P, _P, _P, ctypes.POINTER(RouteNStats)], ctypes.c_int),
+    "rp_sim_route_n_uniform": ([_P, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(RouteNStats)],
+                               ctypes.c_int),
     "rp_ownership_snapshot_create": ([_P, ctypes.POINTER(_P)], ctypes.c_int),
     "rp_ownership_snapshot_info": ([_P, ctypes.POINTER(OwnershipStats), _U64P], ctypes.c_int),
     "rp_ownership_snapshot_destroy": ([_P], ctypes.c_int),

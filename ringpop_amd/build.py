@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libringpop_hip.so")
 SOURCES = ["rp_capi.hip", "rp_ring.hip", "rp_sim.hip", "rp_route.hip", "rp_traffic.hip", "rp_own.hip", "rp_repl.hip", "rp_xport.hip",
-           "rp_node.hip", "rp_calib.hip", "rp_hold.hip"]
+           "rp_node.hip", "rp_calib.hip", "rp_hold.hip", "rp_routen.hip"]
 _INCLUDE_RE = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)
 
 
@@ -38,6 +38,10 @@ HEADERS = included_headers()
 ARCH = os.environ.get("RINGPOP_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-Wall", "-Wno-unused-function"]
+# Flags of single sources, after FLAGS: translation units written since keep the
+# compiler from forming packed fp32 operations (the older ones keep the flags
+# their code objects were measured with).
+SOURCE_FLAGS = {"rp_routen.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 # Builds of the same sources with other compile-time settings, each its own
 # library next to the product (loaded through RINGPOP_HIP_LIB):
 #  diag -- in-kernel cycle stamps (RP_DIAG);
@@ -64,7 +68,7 @@ def _mtime(p):
 def _stamp(flags):
     """What the objects depend on besides the sources: compiler, arch, flags."""
     return json.dumps({"hipcc": os.path.realpath(HIPCC), "arch": ARCH, "flags": flags,
-                       "sources": SOURCES}, sort_keys=True)
+                       "sources": SOURCES, "source_flags": SOURCE_FLAGS}, sort_keys=True)
 
 
 def variant_lib(variant):
@@ -92,7 +96,7 @@ def build(force=False, verbose=False, diag=False, variant=None):
         o = os.path.join(obj_dir, src.replace(".hip", ".o"))
         objs.append(o)
         if force or _mtime(o) < max(_mtime(s), hdr_time):
-            jobs.append([HIPCC, *flags, "-c", s, "-o", o])
+            jobs.append([HIPCC, *flags, *SOURCE_FLAGS.get(src, []), "-c", s, "-o", o])
 
     def run(cmd):
         if verbose:

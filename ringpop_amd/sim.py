@@ -3,7 +3,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (MovementStats, OwnershipStats, ReplicationStats, RequestPending, RequestResult, RoundStats, RouteStats, SimConfig, TrafficConfig, TrafficStats, check,
+from ._lib import (MovementStats, OwnershipStats, ReplicationStats, RequestPending, RequestResult, RoundStats, RouteNStats, RouteStats, SimConfig, TrafficConfig, TrafficStats, check,
                    lib, ptr)
 
 KERNEL_CATEGORIES = ("churn", "issue", "merge_ping", "merge_resp", "checksum", "other")
@@ -499,6 +499,39 @@ class Sim:
         check(lib().rp_sim_holders_at(self._h, int(replicas), ptr(h), len(h), int(cap), ptr(out) if out.size else None,
                                       ptr(counts)))
         return out, counts
+
+    # ---- replicated requests between rounds (rp_sim_route_n)
+    ROUTE_N_EMPTY = 255  # the outcome of a slot past the end of the entry's list
+
+    def route_n(self, replicas, entries, key_hashes):
+        """Request i enters at node entries[i] and is sent to every owner of
+        lookupN(key_hashes[i], replicas) in the entry's view, with the next
+        round's clock: (dests int32 [n, R], outcomes uint8 [n, R] (indices into
+        ROUTE_OUTCOMES, ROUTE_N_EMPTY past the list's end), holds uint8 [n, R]
+        (the destination believes it is a replica), acks uint8 [n], stats
+        dict)."""
+        e = np.ascontiguousarray(entries, dtype=np.uint32)
+        h = np.ascontiguousarray(key_hashes, dtype=np.uint32)
+        R = int(replicas)
+        if e.ndim != 1 or e.shape != h.shape:
+            raise ValueError("route_n: two arrays of one length")
+        cols = max(R, 0)
+        dests = np.zeros((len(e), cols), dtype=np.int32)
+        outcomes = np.zeros((len(e), cols), dtype=np.uint8)
+        holds = np.zeros((len(e), cols), dtype=np.uint8)
+        acks = np.zeros(len(e), dtype=np.uint8)
+        st = RouteNStats()
+        check(lib().rp_sim_route_n(self._h, R & 0xFFFFFFFF, ptr(e), ptr(h), len(e), ptr(dests), ptr(outcomes), ptr(holds),
+                                   ptr(acks), ctypes.byref(st)))
+        return dests, outcomes, holds, acks, st.as_dict()
+
+    def route_n_uniform(self, replicas, seed, count):
+        """The stats of route_n() for `count` requests drawn on the device from
+        splitmix64(seed) (rp_sim_route_n_uniform)."""
+        st = RouteNStats()
+        check(lib().rp_sim_route_n_uniform(self._h, int(replicas) & 0xFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF, int(count),
+                                           ctypes.byref(st)))
+        return st.as_dict()
 
     # ---- ownership movement between two instants (rp_sim_ownership_moved; DESIGN.md §15)
     def ownership_snapshot(self):
