@@ -604,6 +604,72 @@ int rp_sim_replication_at(rp_sim *sim, uint32_t replicas, const uint32_t *key_ha
 int rp_sim_holders_at(rp_sim *sim, uint32_t replicas, const uint32_t *key_hashes, size_t nkeys, size_t cap,
                       int32_t *holders, uint32_t *counts);
 
+/* ---- Replica-set movement between two instants --------------------------------
+ * Which replicas changed hands: ownership movement above for
+ * the sets the replica-set census counts.  A snapshot fixes, at the clock it
+ * is taken and for its R in [1, 8], the held set H(v) of every node v: the
+ * intervals v holds at R in the census' sense -- none for a node that is no
+ * claimant, every interval for an empty ring or a ring of v alone.  It owns
+ * its device buffers (per node up to 100 arcs, and claims_R(i): about 79 MB
+ * at 65,536 nodes); any number may be live, at any mix of R and beside
+ * ownership snapshots, and a snapshot and its simulation may be destroyed in
+ * either order.  rp_replication_snapshot_info: the census' stats at the
+ * snapshot, its clock and its R (each may be NULL).
+ *
+ * rp_sim_replication_moved compares `from` with `to`, or with the simulation
+ * as it is now at from's R when `to` is NULL (through the replica census'
+ * cache: without a call that can change a ring in between, the current arcs
+ * are recorded once).  Node v gains H_to(v) \ H_from(v) and loses the reverse;
+ * gained[v] and lost[v] (each NULL, or cap >= n entries) are the numbers of
+ * hashes in them -- the sum of gained[] is the volume of copies to ship.  Per
+ * interval i, g(i) nodes gain it and l(i) lose it, and claims_to(i) =
+ * claims_from(i) + g(i) - l(i).  In the stats
+ *   transition[a][b]  hashes whose claims_from is under (a = 0: < R), exact
+ *                     (1: = R) or over (2: > R) and whose claims_to is b (the
+ *                     nine sum to 2^32);
+ *   same_set          hashes with g = l = 0;
+ *   kept_none         hashes with claims_from > 0 and l = claims_from: no node
+ *                     that held them at `from` still holds them at `to`;
+ *   kept_none_regained  those of them with g > 0: new holders, and no
+ *                     surviving believer to copy from;
+ *   gained, lost, gainers, losers, max_gained(_node), max_lost(_node),
+ *   max_turnover(_hash), from_clock, to_clock, intervals  as in
+ *                     rp_movement_stats; replicas is R.
+ * With R = 1 every field shared with rp_movement_stats, gained[] and lost[]
+ * equal rp_sim_ownership_moved's, and kept_none >= handed_off.
+ *
+ * rp_sim_replication_moved_at: for each key hash, which nodes hold it at `to`
+ * and not at `from` (gainers) and the reverse (losers).  n_gained[k] and
+ * n_lost[k] are the full numbers, g and l of the key's interval, whatever cap
+ * is; gainers and losers are [nkeys * cap], row k the min(cap, count) lowest
+ * node ids in ascending order, unused slots -1; either list may be NULL (the
+ * counts only).  Deterministic.
+ *
+ * Exact, on the device: the comparison in time proportional to the ring's
+ * points, the per-key query to nodes x keys.  Errors: RP_ERR_UNSUPPORTED on
+ * one rank of a multi-process or loop cluster; RP_ERR_INVALID for R outside
+ * [1, 8], a snapshot of another simulation, a `to` at another R than `from`,
+ * a null sim, stats, from, key_hashes or count array, or cap < n for gained /
+ * lost; RP_ERR_STATE for a snapshot taken before rp_sim_load_addresses
+ * changed the points.  Neither census' results change. */
+typedef struct rp_replication_snapshot rp_replication_snapshot;
+typedef struct {
+    uint64_t transition[3][3];
+    uint64_t same_set, kept_none, kept_none_regained, gained, lost, gainers, losers;
+    uint64_t max_gained, max_gained_node, max_lost, max_lost_node, max_turnover, max_turnover_hash;
+    uint64_t from_clock, to_clock, intervals, replicas;
+    uint64_t reserved[6];
+} rp_replica_movement_stats;
+int rp_replication_snapshot_create(rp_sim *sim, uint32_t replicas, rp_replication_snapshot **out);
+int rp_replication_snapshot_info(const rp_replication_snapshot *snap, rp_replication_stats *stats, uint64_t *clock,
+                                 uint32_t *replicas);
+int rp_replication_snapshot_destroy(rp_replication_snapshot *snap);
+int rp_sim_replication_moved(rp_sim *sim, const rp_replication_snapshot *from, const rp_replication_snapshot *to,
+                             rp_replica_movement_stats *stats, uint64_t *gained, uint64_t *lost, size_t cap);
+int rp_sim_replication_moved_at(rp_sim *sim, const rp_replication_snapshot *from, const rp_replication_snapshot *to,
+                                const uint32_t *key_hashes, size_t nkeys, size_t cap, int32_t *gainers, int32_t *losers,
+                                uint32_t *n_gained, uint32_t *n_lost);
+
 /* ---- Replicated requests (between rounds) --------------------------------------
  * rp_sim_route_n: what a service that sends a request for a key to all of its
  * R replicas sees.  Request i enters the cluster at node

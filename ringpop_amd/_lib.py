@@ -101,6 +101,21 @@ class MovementStats(ctypes.Structure):
         return d
 
 
+REPLICA_MOVEMENT_SCALARS = ("same_set", "kept_none", "kept_none_regained", "gained", "lost", "gainers", "losers",
+                            "max_gained", "max_gained_node", "max_lost", "max_lost_node", "max_turnover",
+                            "max_turnover_hash", "from_clock", "to_clock", "intervals", "replicas")
+
+
+class ReplicaMovementStats(ctypes.Structure):
+    _fields_ = ([("transition", ctypes.c_uint64 * 3 * 3)] + [(k, ctypes.c_uint64) for k in REPLICA_MOVEMENT_SCALARS] +
+                [("reserved", ctypes.c_uint64 * 6)])
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in REPLICA_MOVEMENT_SCALARS}
+        d["transition"] = [[int(x) for x in row] for row in self.transition]
+        return d
+
+
 class TrafficConfig(ctypes.Structure):
     _fields_ = [("max_retries", ctypes.c_int32), ("nschedule", ctypes.c_uint32), ("schedule", ctypes.c_uint32 * 8),
                 ("enforce_consistency", ctypes.c_int32), ("track", ctypes.c_uint32), ("timing", ctypes.c_uint32),
@@ -232,6 +247,11 @@ SIGNATURES = {
     "rp_ownership_snapshot_info": ([_P, ctypes.POINTER(OwnershipStats), _U64P], ctypes.c_int),
     "rp_ownership_snapshot_destroy": ([_P], ctypes.c_int),
     "rp_sim_ownership_moved": ([_P, _P, _P, ctypes.POINTER(MovementStats), _P, _P, _SZ], ctypes.c_int),
+    "rp_replication_snapshot_create": ([_P, ctypes.c_uint32, ctypes.POINTER(_P)], ctypes.c_int),
+    "rp_replication_snapshot_info": ([_P, ctypes.POINTER(ReplicationStats), _U64P, _U32P], ctypes.c_int),
+    "rp_replication_snapshot_destroy": ([_P], ctypes.c_int),
+    "rp_sim_replication_moved": ([_P, _P, _P, ctypes.POINTER(ReplicaMovementStats), _P, _P, _SZ], ctypes.c_int),
+    "rp_sim_replication_moved_at": ([_P, _P, _P, _P, _SZ, _SZ, _P, _P, _P, _P], ctypes.c_int),
     "rp_traffic_create": ([_P, ctypes.POINTER(TrafficConfig), ctypes.POINTER(_P)], ctypes.c_int),
     "rp_traffic_destroy": ([_P], ctypes.c_int),
     "rp_traffic_submit": ([_P, _P, _P, _SZ, _U64P], ctypes.c_int),

@@ -403,7 +403,18 @@ struct rp_sim {
     rp::DevBuf<int32_t> rep_diff, rep_tile;
     rp::DevBuf<unsigned long long> rep_held, rep_out;
     rp_replication_stats rep_stats{};
-    void rep_refresh(uint32_t replicas);
+    // replica-set movement (rp_replication_snapshot_* / rp_sim_replication_moved
+    // / rp_sim_replication_moved_at; rp_rmove.hip).  A census
+    // run for a snapshot or a comparison also records every node's arcs at
+    // its R (rep_arcs_valid: they are the cached census'); the plain census
+    // never does.  The comparison's scratch is the ownership comparison's
+    // (mv_diff, mv_tile, mv_gained, mv_lost); its results have a buffer of
+    // their own.
+    bool rep_arcs_valid = false;
+    rp::DevBuf<uint32_t> rep_arc_n;  // n: arcs recorded, or OWN_ARC_ALL
+    rp::DevBuf<uint2> rep_arcs;      // n x REPLICAS: (q, p) by ascending p
+    rp::DevBuf<unsigned long long> rmv_out;
+    void rep_refresh(uint32_t replicas, bool record = false);
     template <bool UNIFORM>
     void route_launch(const uint32_t* entries, const uint32_t* keys, uint64_t seed, uint64_t count, int32_t* dests,
                       uint8_t* outcomes, uint8_t* agrees, rp_route_stats* stats);

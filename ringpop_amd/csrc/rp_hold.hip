@@ -174,6 +174,12 @@ __global__ void __launch_bounds__(HOLD_BLOCK) k_hold_list(const unsigned long lo
     for (uint32_t i = (base < cap ? base : cap) + lane; i < cap; i += 64) row[i] = -1;
 }
 
+void hold_list(const unsigned long long* mask, uint32_t nk, uint32_t tiles, uint32_t cap, int32_t* holders, uint32_t* counts,
+               hipStream_t st) {
+    hipLaunchKernelGGL(k_hold_list, dim3((nk + HOLD_WAVES - 1) / HOLD_WAVES), dim3(HOLD_BLOCK), 0, st, mask, nk, tiles, cap,
+                       holders, counts);
+}
+
 }  // namespace rp
 
 // =====================================================================
@@ -219,8 +225,7 @@ int rp_sim_holders_at(rp_sim* c, uint32_t replicas, const uint32_t* key_hashes, 
             });
             RP_HIP(hipGetLastError());
             s0.timed(5, [&] {
-                hipLaunchKernelGGL(rp::k_hold_list, dim3((m + rp::HOLD_WAVES - 1) / rp::HOLD_WAVES), dim3(rp::HOLD_BLOCK), 0,
-                                   s0.st, (const unsigned long long*)dmask.p, m, tiles, (uint32_t)dcap, drow.p, dcnt.p);
+                rp::hold_list(dmask.p, m, tiles, (uint32_t)dcap, drow.p, dcnt.p, s0.st);
             });
             RP_HIP(hipGetLastError());
             if (dcap == cap && cap)

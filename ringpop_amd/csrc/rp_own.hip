@@ -22,7 +22,6 @@ namespace rp {
 // (claims << 32 | ~index, so that an atomic max keeps the lowest index)
 enum : uint32_t { OWN_MEASURE = 0, OWN_CLAIMANTS = 8, OWN_MAX = 9, OWN_NOUT = 10 };
 constexpr uint32_t OWN_WALK_STEPS = 4;  // backward steps a lane takes alone before the wave searches for it
-constexpr uint32_t OWN_ARC_ALL = 0x80000000u;  // a recorded arc count: the node claims every interval
 
 // replica hash -> index of its point (every replica hash is a point: the
 // search is exact).  The host sorted each server's hashes, so a row's indices
@@ -232,30 +231,6 @@ __global__ void __launch_bounds__(256) k_own_at(OwnArgs A, const uint32_t* keys,
 }
 
 // ---- ownership movement between two instants (rp_sim_ownership_moved)
-
-// the comparison's device results: rp_movement_stats' transition[3][3] and
-// measures, the per-node sums and counts, and three packed maxima
-enum : uint32_t {
-    MV_TRANS = 0, MV_SAME = 9, MV_HANDED = 10, MV_GAINED = 11, MV_LOST = 12, MV_GAINERS = 13, MV_LOSERS = 14,
-    MV_MAXG = 15, MV_MAXL = 16, MV_MAXT = 17, MV_NOUT = 18
-};
-constexpr uint32_t MV_SEGS = OWN_REPLICAS + 1;  // a side's arcs as index segments: the wrapping arc is two
-constexpr uint32_t MV_WAVES = OWN_BLOCK / 64;
-constexpr uint32_t MV_NODE_MASK = 0x7FFFFFFFu;
-
-struct MoveArgs {
-    // side 0: from, side 1: to -- recorded arcs (k_own_arcs<true>) and claims
-    const uint32_t* arc_n[2];
-    const uint2* arcs[2];
-    const uint32_t* claims[2];
-    const uint32_t* pt_hash;
-    uint32_t n, npts, ntiles;
-    int32_t* diff;               // 2 x (npts + 1): the gains' difference array, then the losses'
-    int32_t* tile_sum;           // 2 x ntiles
-    unsigned long long* gained;  // n
-    unsigned long long* lost;    // n
-    unsigned long long* out;     // MV_NOUT
-};
 
 // a node's measure (0 .. 2^32) with its id, so that an atomic max keeps the
 // lowest id among equals; the measure needs 33 bits, which leaves 31 for the id
@@ -494,6 +469,12 @@ void own_scan_tiles(const OwnArgs& A, hipStream_t st) {
     hipLaunchKernelGGL(k_own_tile_scan, dim3(1), dim3(64), 0, st, A);
 }
 
+void move_scan(const MoveArgs& A, hipStream_t st) {
+    hipLaunchKernelGGL(k_move_arcs, dim3((A.n + MV_WAVES - 1) / MV_WAVES), dim3(OWN_BLOCK), 0, st, A);
+    hipLaunchKernelGGL(k_move_tile_sums, dim3(A.ntiles, 2), dim3(OWN_BLOCK), 0, st, A);
+    hipLaunchKernelGGL(k_move_tile_scan, dim3(2), dim3(64), 0, st, A);
+}
+
 static unsigned blocks_for(uint64_t items, unsigned per_block, unsigned cap) {
     const uint64_t g = (items + per_block - 1) / per_block;
     return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
@@ -668,6 +649,15 @@ namespace {
 
 std::atomic<uint64_t> g_snapshot_sims{0};
 
+}  // namespace
+
+uint64_t rp::snapshot_sim_id(rp_sim* c) {
+    if (!c->own_id) c->own_id = ++g_snapshot_sims;
+    return c->own_id;
+}
+
+namespace {
+
 void check_snapshot(const rp_sim* c, const rp_ownership_snapshot* s, const char* which) {
     if (s->sim_id != c->own_id) throw Error(RP_ERR_INVALID, std::string(which) + ": a snapshot of another simulation");
     if (s->gen != c->own_gen || s->n != c->n || s->npts != c->sh.front()->npts)
@@ -683,10 +673,9 @@ int rp_ownership_snapshot_create(rp_sim* c, rp_ownership_snapshot** out) {
         if (!c || !out) throw Error(RP_ERR_INVALID, "null pointer");
         *out = nullptr;
         c->own_refresh(true);
-        if (!c->own_id) c->own_id = ++g_snapshot_sims;
         Shard& s0 = *c->sh.front();
         std::unique_ptr<rp_ownership_snapshot> s(new rp_ownership_snapshot());
-        s->sim_id = c->own_id; s->gen = c->own_gen; s->clock = c->round;
+        s->sim_id = rp::snapshot_sim_id(c); s->gen = c->own_gen; s->clock = c->round;
         s->dev = c->dev; s->n = c->n; s->npts = s0.npts;
         s->stats = c->own_stats;
         s->arc_n.alloc(c->own_arc_n.n);
@@ -752,9 +741,7 @@ int rp_sim_ownership_moved(rp_sim* c, const rp_ownership_snapshot* from, const r
         s0.timed(5, [&] {
             RP_HIP(hipMemsetAsync(c->mv_diff.p, 0, c->mv_diff.bytes(), s0.st));
             RP_HIP(hipMemsetAsync(c->mv_out.p, 0, c->mv_out.bytes(), s0.st));
-            hipLaunchKernelGGL(rp::k_move_arcs, dim3((n + rp::MV_WAVES - 1) / rp::MV_WAVES), dim3(rp::OWN_BLOCK), 0, s0.st, A);
-            hipLaunchKernelGGL(rp::k_move_tile_sums, dim3(ntiles, 2), dim3(rp::OWN_BLOCK), 0, s0.st, A);
-            hipLaunchKernelGGL(rp::k_move_tile_scan, dim3(2), dim3(64), 0, s0.st, A);
+            rp::move_scan(A, s0.st);
             hipLaunchKernelGGL(rp::k_move_finish, dim3(ntiles), dim3(rp::OWN_BLOCK), 0, s0.st, A);
         });
         RP_HIP(hipGetLastError());

@@ -16,6 +16,14 @@ constexpr uint32_t REP_MAX_N = 16;       // owners of a per-view lookupN
 constexpr uint32_t REP_SOLO_EXTRA = 3;   // a lane examines target + 3 points alone before the wave walks for it
 constexpr uint32_t REP_NONE = 0xFFFFFFFFu;  // a walk that went once round without ending
 
+// k_hold_list (rp_hold.hip) on st: one wave per key over its row of `tiles`
+// 64-bit words, bit b of word t standing for node t * 64 + b -- counts[key] =
+// the bits set, holders[key * cap ..] the first `cap` of their nodes in
+// ascending order, the remaining slots -1.  The holders query's second kernel,
+// which replica-set movement (rp_rmove.hip; §19) runs on its gain and loss masks.
+void hold_list(const unsigned long long* mask, uint32_t nk, uint32_t tiles, uint32_t cap, int32_t* holders, uint32_t* counts,
+               hipStream_t st);
+
 // The distinct owners a walk has kept, in order of first appearance: K
 // registers, written and compared by unrolled chains of selects (constant
 // indices only: nothing spills to scratch).  Empty slots hold -2, which no

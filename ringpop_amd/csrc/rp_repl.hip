@@ -41,13 +41,26 @@ constexpr uint32_t REP_NOUT = REP_WORK + REP_WORK_SLOTS * REP_WORK_STRIDE;
 // are answered without a walk.  A lane examines R + REP_SOLO_EXTRA points
 // alone, then walk_wave takes over: the work of a wave is bounded by
 // 100 (R + 3) + (npts + 100 x 63) / 64 + 100 R steps whatever the view.
-__global__ void __launch_bounds__(OWN_BLOCK) k_rep_arcs(OwnArgs A, uint32_t R) {
+//
+// REC (a snapshot, or a comparison with the simulation as it is: DESIGN.md
+// §19) also writes the arcs as (q, p) to the node's row of `arcs`, in
+// ascending p, once both walks of a pass have ended and the wave is converged
+// -- a pass' arcs ranked by a ballot, the second pass after the first -- and
+// their number to arc_n[v]: 0 for a node that is no claimant, OWN_ARC_ALL for
+// one that holds everything (an empty ring, a ring of v alone, a whole turn).
+// The plain census launches k_rep_arcs<false> (arc_n = arcs = nullptr), whose
+// instructions are those of the kernel before it became a template.
+template <bool REC>
+__global__ void __launch_bounds__(OWN_BLOCK) k_rep_arcs(OwnArgs A, uint32_t R, uint32_t* arc_n, uint2* arcs) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t v = blockIdx.x * (OWN_BLOCK / 64) + (threadIdx.x >> 6);
     if (v >= A.n) return;  // (the whole wave)
     const uint32_t g = v / A.nl;
     if (A.dead[g][v] != 0) {  // fail-stopped, or not joined yet: no claimant
-        if (lane == 0) A.claimed[v] = 0;
+        if (lane == 0) {
+            A.claimed[v] = 0;
+            if (REC) arc_n[v] = 0;
+        }
         return;
     }
     const RouteShard& t = A.tab[g];
@@ -61,12 +74,14 @@ __global__ void __launch_bounds__(OWN_BLOCK) k_rep_arcs(OwnArgs A, uint32_t R) {
         if (lane == 0) {
             atomicAdd(&A.diff[0], 1);
             A.claimed[v] = 1ull << 32;
+            if (REC) arc_n[v] = OWN_ARC_ALL;
         }
         return;
     }
     const uint32_t* row = A.srv_pt + (size_t)v * OWN_REPLICAS;
     unsigned long long total = 0;
-    uint32_t solo = 0, coop = 0, arcs = 0;
+    uint32_t solo = 0, coop = 0, narc = 0;
+    uint32_t kept = 0;  // REC: arcs stored so far, or OWN_ARC_ALL
     for (uint32_t r0 = 0; r0 < OWN_REPLICAS; r0 += 64) {
         const uint32_t rr = r0 + lane;
         bool search = false;
@@ -84,7 +99,7 @@ __global__ void __launch_bounds__(OWN_BLOCK) k_rep_arcs(OwnArgs A, uint32_t R) {
         solo += dist;
         coop += walk_wave<REP_MAX_R - 1, true>(ring, A, u, pos, dist, !done, q, (int32_t)v, R, lane);
         if (search) {
-            arcs++;
+            narc++;
             if (q == p || q == REP_NONE) {  // the view's only own point (the walk ends at p at the latest)
                 atomicAdd(&A.diff[0], 1);
                 total += 1ull << 32;
@@ -95,12 +110,22 @@ __global__ void __launch_bounds__(OWN_BLOCK) k_rep_arcs(OwnArgs A, uint32_t R) {
                 total += (uint32_t)(A.pt_hash[p] - A.pt_hash[q]);
             }
         }
+        if (REC) {
+            // (p ascends with the lane: the rank among the pass' searching lanes is the arc's place)
+            const bool whole = search && (q == p || q == REP_NONE);
+            const unsigned long long arc = __ballot(search && !whole);
+            if (__ballot(whole)) kept = OWN_ARC_ALL;
+            if (search && !whole)
+                arcs[(size_t)v * OWN_REPLICAS + (kept & ~OWN_ARC_ALL) + __popcll(arc & ((1ull << lane) - 1))] = make_uint2(q, p);
+            kept += (uint32_t)__popcll(arc);
+        }
     }
     total = wave_sum_u64(total);
     const unsigned long long steps = wave_sum_u64(solo);
-    const unsigned long long narcs = wave_sum_u64(arcs);
+    const unsigned long long narcs = wave_sum_u64(narc);
     if (lane == 0) {
         A.claimed[v] = total;
+        if (REC) arc_n[v] = (kept & OWN_ARC_ALL) ? OWN_ARC_ALL : kept;
         atomicAdd(&A.out[REP_WORK + (v % REP_WORK_SLOTS) * REP_WORK_STRIDE], narcs << 40 | (steps + coop));
     }
 }
@@ -226,12 +251,19 @@ static rp::OwnArgs rep_args(rp_sim* c) {
 
 // The replica census for R, unless it is the cached one and no call that can
 // change a ring ran since (timed as "other", like a route).
-void rp_sim::rep_refresh(uint32_t R) {
+// record: the arcs are wanted too (§19) -- a cached census that did not
+// record them runs again, with the recording kernel.
+void rp_sim::rep_refresh(uint32_t R, bool record) {
     own_prepare();
     Shard& s0 = *sh.front();
     const uint32_t npts = s0.npts;
-    if (!rep_stale && rep_r == R && rep_claims.n == npts && rep_held.n == n) return;
+    if (!rep_stale && rep_r == R && rep_claims.n == npts && rep_held.n == n && (!record || rep_arcs_valid)) return;
     rep_r = 0;  // (nothing is cached until this run is complete)
+    rep_arcs_valid = false;
+    if (record) {
+        if (rep_arc_n.n != n) rep_arc_n.alloc(n);
+        if (rep_arcs.n != (size_t)n * rp::OWN_REPLICAS) rep_arcs.alloc((size_t)n * rp::OWN_REPLICAS);
+    }
     if (rep_diff.n != (size_t)npts + 1) rep_diff.alloc((size_t)npts + 1);
     if (rep_claims.n != npts) rep_claims.alloc(npts);
     if (rep_held.n != n) rep_held.alloc(n);
@@ -244,7 +276,12 @@ void rp_sim::rep_refresh(uint32_t R) {
         RP_HIP(hipMemsetAsync(rep_out.p, 0, rep_out.bytes(), s0.st));
         RP_HIP(hipMemsetAsync(rep_out.p + rp::REP_MIN, 0xFF, sizeof(unsigned long long), s0.st));
         const unsigned per = rp::OWN_BLOCK / 64;  // views (waves) per block
-        hipLaunchKernelGGL(rp::k_rep_arcs, dim3((n + per - 1) / per), dim3(rp::OWN_BLOCK), 0, s0.st, A, R);
+        if (record)
+            hipLaunchKernelGGL(rp::k_rep_arcs<true>, dim3((n + per - 1) / per), dim3(rp::OWN_BLOCK), 0, s0.st, A, R,
+                               rep_arc_n.p, rep_arcs.p);
+        else
+            hipLaunchKernelGGL(rp::k_rep_arcs<false>, dim3((n + per - 1) / per), dim3(rp::OWN_BLOCK), 0, s0.st, A, R,
+                               (uint32_t*)nullptr, (uint2*)nullptr);
         rp::own_scan_tiles(A, s0.st);
         hipLaunchKernelGGL(rp::k_rep_finish, dim3(ntiles), dim3(rp::OWN_BLOCK), 0, s0.st, A);
     });
@@ -278,6 +315,7 @@ void rp_sim::rep_refresh(uint32_t R) {
     rep_stats = st;
     rep_r = R;
     rep_stale = false;
+    rep_arcs_valid = record;
 }
 
 extern "C" {

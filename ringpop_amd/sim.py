@@ -3,7 +3,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (MovementStats, OwnershipStats, ReplicationStats, RequestPending, RequestResult, RoundStats, RouteNStats, RouteStats, SimConfig, TrafficConfig, TrafficStats, check,
+from ._lib import (MovementStats, OwnershipStats, ReplicaMovementStats, ReplicationStats, RequestPending, RequestResult, RoundStats, RouteNStats, RouteStats, SimConfig, TrafficConfig, TrafficStats, check,
                    lib, ptr)
 
 KERNEL_CATEGORIES = ("churn", "issue", "merge_ping", "merge_resp", "checksum", "other")
@@ -145,6 +145,40 @@ class OwnershipSnapshot:
     def close(self):
         if self._h:
             lib().rp_ownership_snapshot_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ReplicationSnapshot:
+    """rp_replication_snapshot: every node's held set at `replicas` replicas
+    at one clock (Sim.replication_snapshot).  `clock` is the
+    round count it was taken at, `stats` the replica census' stats dict then.
+    It owns its device buffers: close it (or use it as a context manager) when
+    done; it may outlive its Sim."""
+
+    def __init__(self, sim, replicas):
+        self._h = ctypes.c_void_p()
+        check(lib().rp_replication_snapshot_create(sim._h, int(replicas) & 0xFFFFFFFF, ctypes.byref(self._h)))
+        st, clock, r = ReplicationStats(), ctypes.c_uint64(0), ctypes.c_uint32(0)
+        check(lib().rp_replication_snapshot_info(self._h, ctypes.byref(st), ctypes.byref(clock), ctypes.byref(r)))
+        self.stats = st.as_dict()
+        self.clock = int(clock.value)
+        self.replicas = int(r.value)
+
+    def close(self):
+        if self._h:
+            lib().rp_replication_snapshot_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __enter__(self):
@@ -554,6 +588,47 @@ class Sim:
         d["gained_by"] = gained
         d["lost_by"] = lost
         return d
+
+    # ---- replica-set movement between two instants (rp_sim_replication_moved)
+    def replication_snapshot(self, replicas):
+        """Every node's held set at `replicas` replicas now, to compare later
+        (a ReplicationSnapshot)."""
+        return ReplicationSnapshot(self, replicas)
+
+    def replication_moved(self, frm, to=None):
+        """Which replicas changed hands between snapshot `frm` and snapshot
+        `to` (None: the simulation as it is now, at frm's replicas): a dict of
+        rp_replica_movement_stats' fields (`transition` as 3 x 3 lists over
+        under / exact / over) plus `gained_by` and `lost_by`: per node the
+        hashes it holds at `to` and not at `frm`, and the reverse, as uint64
+        arrays whose sums are the stats' `gained` (the copies to ship) and
+        `lost`."""
+        st = ReplicaMovementStats()
+        gained = np.zeros(self.n, dtype=np.uint64)
+        lost = np.zeros(self.n, dtype=np.uint64)
+        check(lib().rp_sim_replication_moved(self._h, frm._h, to._h if to is not None else None, ctypes.byref(st),
+                                             ptr(gained), ptr(lost), self.n))
+        d = st.as_dict()
+        d["gained_by"] = gained
+        d["lost_by"] = lost
+        return d
+
+    def replication_moved_at(self, frm, to, hashes, cap=16):
+        """Per key hash, which nodes hold it at `to` (None: now) and not at
+        `frm`, and the reverse: (gainers int32 [nk, cap], losers int32
+        [nk, cap], each row the lowest node ids in ascending order, unused
+        slots -1; n_gained uint32 [nk], n_lost uint32 [nk], the full numbers
+        whatever `cap`)."""
+        h = np.ascontiguousarray(hashes, dtype=np.uint32)
+        if h.ndim != 1 or int(cap) < 0:
+            raise ValueError("replication_moved_at: one array of key hashes and a row length >= 0")
+        gainers = np.full((len(h), int(cap)), -1, dtype=np.int32)
+        losers = np.full((len(h), int(cap)), -1, dtype=np.int32)
+        ng, nl = np.zeros(len(h), dtype=np.uint32), np.zeros(len(h), dtype=np.uint32)
+        check(lib().rp_sim_replication_moved_at(self._h, frm._h, to._h if to is not None else None, ptr(h), len(h), int(cap),
+                                                ptr(gainers) if gainers.size else None,
+                                                ptr(losers) if losers.size else None, ptr(ng), ptr(nl)))
+        return gainers, losers, ng, nl
 
     def traffic(self, **cfg):
         """A request tracker on this simulation (rp_traffic_create): max_retries=3,
