@@ -670,6 +670,52 @@ int rp_sim_replication_moved_at(rp_sim *sim, const rp_replication_snapshot *from
                                 const uint32_t *key_hashes, size_t nkeys, size_t cap, int32_t *gainers, int32_t *losers,
                                 uint32_t *n_gained, uint32_t *n_lost);
 
+/* ---- Membership census (between rounds) -----------------------------------------
+ * How every live node sees each member: the question before the
+ * rings'.  The viewers are the claimants of the ownership census -- the nodes
+ * that are neither fail-stopped nor still outside the cluster; a node that
+ * left gracefully is one.  vs(v, a) = incarnation << 3 | status is viewer v's
+ * cell for member a, 0 where v does not know a; the merge rules' precedence
+ * (alive < suspect < faulty < leave at one incarnation) is its unsigned order,
+ * so the newest state of a member is the 64-bit maximum.
+ *   seen[a * 5 + s]  viewers whose cell for a has status s (0 absent, 1 alive,
+ *                    2 suspect, 3 faulty, 4 leave); the five sum to viewers
+ *   top[a]           the maximum of vs(v, a) over the viewers, 0: none knows a
+ *   at_top[a]        viewers with vs(v, a) == top[a]
+ *   behind[v]        members a with vs(v, a) != top[a]; 0 when v is no viewer
+ * seen is [n * 5], the others [n]; each may be NULL, stats may be NULL when an
+ * array is given, and cap is the entries (rows of seen) the arrays hold.  In
+ * the stats
+ *   viewers, members        the viewers, and n
+ *   agreed                  members with at_top == viewers
+ *   cells_behind            the sum over members of viewers - at_top: the sum
+ *                           of behind[]
+ *   max_behind_member(_id)  the largest viewers - at_top[a], the first such a
+ *   laggards                viewers with behind > 0
+ *   max_behind_viewer(_id)  the largest behind[v], the first such v
+ *   undetected, suspected_dead  over fail-stopped members: the viewers that
+ *                           hold them alive, suspect
+ *   false_faulty, false_suspect, unknown  over members that are viewers: the
+ *                           viewers that hold them faulty, suspect, absent
+ *
+ * Exact, on the device, two reads of the view matrix (one when neither stats
+ * nor behind is asked for), recomputed at every call: nothing is cached, no
+ * census or ring checksum is read or invalidated, and the simulation runs on
+ * as if the call had not been made.  It needs every node's view on this
+ * process's device: RP_ERR_UNSUPPORTED on one rank of a multi-process or loop
+ * cluster; in-process shards give the one-shard result.  RP_ERR_INVALID for a
+ * null sim, no output at all, or cap < n with an array given; a refused call
+ * writes nothing. */
+typedef struct {
+    uint64_t viewers, members, agreed, cells_behind;
+    uint64_t max_behind_member, max_behind_member_id;
+    uint64_t laggards, max_behind_viewer, max_behind_viewer_id;
+    uint64_t undetected, suspected_dead, false_faulty, false_suspect, unknown;
+    uint64_t reserved[2];
+} rp_membership_stats;
+int rp_sim_membership(rp_sim *sim, rp_membership_stats *stats, uint32_t *seen, uint64_t *top, uint32_t *at_top,
+                      uint32_t *behind, size_t cap);
+
 /* ---- Replicated requests (between rounds) --------------------------------------
  * rp_sim_route_n: what a service that sends a request for a key to all of its
  * R replicas sees.  Request i enters the cluster at node

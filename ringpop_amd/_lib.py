@@ -116,6 +116,18 @@ class ReplicaMovementStats(ctypes.Structure):
         return d
 
 
+MEMBERSHIP_SCALARS = ("viewers", "members", "agreed", "cells_behind", "max_behind_member", "max_behind_member_id",
+                      "laggards", "max_behind_viewer", "max_behind_viewer_id", "undetected", "suspected_dead",
+                      "false_faulty", "false_suspect", "unknown")
+
+
+class MembershipStats(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint64) for k in MEMBERSHIP_SCALARS] + [("reserved", ctypes.c_uint64 * 2)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in MEMBERSHIP_SCALARS}
+
+
 class TrafficConfig(ctypes.Structure):
     _fields_ = [("max_retries", ctypes.c_int32), ("nschedule", ctypes.c_uint32), ("schedule", ctypes.c_uint32 * 8),
                 ("enforce_consistency", ctypes.c_int32), ("track", ctypes.c_uint32), ("timing", ctypes.c_uint32),
@@ -240,6 +252,7 @@ SIGNATURES = {
     "rp_sim_replication": ([_P, ctypes.c_uint32, ctypes.POINTER(ReplicationStats), _P, _SZ], ctypes.c_int),
     "rp_sim_replication_at": ([_P, ctypes.c_uint32, _P, _SZ, _P], ctypes.c_int),
     "rp_sim_holders_at": ([_P, ctypes.c_uint32, _P, _SZ, _SZ, _P, _P], ctypes.c_int),
+    "rp_sim_membership": ([_P, ctypes.POINTER(MembershipStats), _P, _P, _P, _P, _SZ], ctypes.c_int),
     "rp_sim_route_n": ([_P, ctypes.c_uint32, _P, _P, _SZ, _P, _P, _P, _P, ctypes.POINTER(RouteNStats)], ctypes.c_int),
     "rp_sim_route_n_uniform": ([_P, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(RouteNStats)],
                                ctypes.c_int),

@@ -415,6 +415,14 @@ struct rp_sim {
     rp::DevBuf<uint2> rep_arcs;      // n x REPLICAS: (q, p) by ascending p
     rp::DevBuf<unsigned long long> rmv_out;
     void rep_refresh(uint32_t replicas, bool record = false);
+    // membership census (rp_sim_membership; rp_members.hip):
+    // no cache -- views change every round -- only its buffers, allocated on
+    // first use and dropped with the shards: the column pass' partials (two
+    // uint4 per slab and member), the blocks' records, seen | at_top | behind,
+    // and top followed by the sixteen words of the stats
+    rp::DevBuf<uint4> mem_part;
+    rp::DevBuf<unsigned long long> mem_rec, mem_top;
+    rp::DevBuf<uint32_t> mem_cnt;
     template <bool UNIFORM>
     void route_launch(const uint32_t* entries, const uint32_t* keys, uint64_t seed, uint64_t count, int32_t* dests,
                       uint8_t* outcomes, uint8_t* agrees, rp_route_stats* stats);

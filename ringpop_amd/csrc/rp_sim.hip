@@ -7277,6 +7277,7 @@ int rp_sim_load_addresses(rp_sim* s, const uint8_t* bytes, const uint64_t* off, 
         s->route_dir.release();
         s->own_srv_pt.release();
         s->own_dead.release();
+        s->mem_part.release(); s->mem_rec.release(); s->mem_cnt.release(); s->mem_top.release();
         std::vector<std::string> a(n);
         for (uint32_t i = 0; i < n; i++) {
             if (off[i + 1] < off[i]) throw Error(RP_ERR_INVALID, "offsets must be non-decreasing");

@@ -3,7 +3,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (MovementStats, OwnershipStats, ReplicaMovementStats, ReplicationStats, RequestPending, RequestResult, RoundStats, RouteNStats, RouteStats, SimConfig, TrafficConfig, TrafficStats, check,
+from ._lib import (MembershipStats, MovementStats, OwnershipStats, ReplicaMovementStats, ReplicationStats, RequestPending, RequestResult, RoundStats, RouteNStats, RouteStats, SimConfig, TrafficConfig, TrafficStats, check,
                    lib, ptr)
 
 KERNEL_CATEGORIES = ("churn", "issue", "merge_ping", "merge_resp", "checksum", "other")
@@ -533,6 +533,26 @@ class Sim:
         check(lib().rp_sim_holders_at(self._h, int(replicas), ptr(h), len(h), int(cap), ptr(out) if out.size else None,
                                       ptr(counts)))
         return out, counts
+
+    # ---- membership census between rounds (rp_sim_membership)
+    def membership(self):
+        """How every live node sees each member: a dict of rp_membership_stats'
+        fields and, per member, `seen` (uint32 [n, 5]: the viewers that hold it
+        absent / alive / suspect / faulty / leave), `top_status` (uint8) and
+        `top_incarnation` (uint64) of its newest state in any viewer's view,
+        `at_top` (the viewers that have reached that state); per node `behind`
+        (the members whose newest state it lacks, 0 for a node that is no
+        viewer).  Recomputed at every call."""
+        st = MembershipStats()
+        seen = np.zeros((self.n, 5), dtype=np.uint32)
+        top = np.zeros(self.n, dtype=np.uint64)
+        at_top = np.zeros(self.n, dtype=np.uint32)
+        behind = np.zeros(self.n, dtype=np.uint32)
+        check(lib().rp_sim_membership(self._h, ctypes.byref(st), ptr(seen), ptr(top), ptr(at_top), ptr(behind), self.n))
+        d = st.as_dict()
+        d.update(seen=seen, top_status=(top & np.uint64(7)).astype(np.uint8), top_incarnation=top >> np.uint64(3),
+                 at_top=at_top, behind=behind)
+        return d
 
     # ---- replicated requests between rounds (rp_sim_route_n; DESIGN.md §18)
     ROUTE_N_EMPTY = 255  # the outcome of a slot past the end of the entry's list
