@@ -258,11 +258,35 @@ def test_reference_fixture(rp, golden):
             assert dev.ring.getServerCount() == step["server_count"]
             assert dev.names(dev.ring.lookup_hashes(probes)).tolist() == step["lookups"]
             for n in g["ns"]:
-                if n == 0:
+                if n == 0:  # (the documented difference: no owner, where the fixture holds lookup(key)'s or [])
+                    got, cnt = dev.lookup_n(probes, 0)
+                    assert got.shape == (len(probes), 0) and (cnt == 0).all()
+                    assert {len(r) for r in step["lookupN"]["0"]} <= {0, 1}
                     continue
                 got, cnt = dev.lookup_n(probes, n)
                 rows = [dev.names(got[k, :cnt[k]]).tolist() for k in range(len(probes))]
                 assert rows == step["lookupN"][str(n)], n
                 assert all((got[k, cnt[k]:] == -1).all() for k in range(len(probes))), n
+    finally:
+        dev.close()
+
+
+def test_lookup_n_zero_and_negative(rp):
+    """n = 0 gives no owner on every key (the
+    reference gives one, or none past the largest point:
+    test_ring_edges_cpu.py); a negative n is RP_ERR_INVALID."""
+    sc = rc.scenario("placed_small")
+    dev = Dev(rp, sc.R)
+    try:
+        for c, m, _ in sc.replay():
+            dev.add_remove(c)
+        probes = rc.probes(sc)
+        got, cnt = dev.lookup_n(probes, 0)
+        assert got.shape == (len(probes), 0) and (cnt == 0).all()
+        assert m.lookup_n_padded(probes[:50], 0)[1].tolist() == [0] * 50
+        for n in (-1, -(2**31)):
+            with pytest.raises(rp.RingpopError) as e:
+                dev.lookup_n(probes, n)
+            assert e.value.code == -1, e.value  # RP_ERR_INVALID
     finally:
         dev.close()

@@ -111,7 +111,7 @@ def test_model_and_oracle_match_reference_fixture(golden, fixture):
     and points at 0 and 4294967295 with a present server that owns nothing.
     lookupN for n >= 1 (n = 0: the reference's do-while returns one owner
     unless the key lies past the largest point; this project returns none,
-    INTEGRATION.md section 1 -- recorded in the fixture, not compared)"""
+    INTEGRATION.md section 1 -- test_lookup_n_zero_differs_from_the_reference_on_purpose)"""
     g = golden(fixture)
     R = g["replica_points"]
     if fixture == "ring_edges.json":
@@ -158,6 +158,45 @@ def test_ring_edges_fixture_has_its_edges(golden):
     # the n = 0 divergence is on record: one owner, or none past the largest point
     second = g["steps"][1]
     assert second["lookupN"]["0"][0] == ["C"] and second["lookupN"]["0"][-1] == []
+
+
+def test_lookup_n_zero_differs_from_the_reference_on_purpose(golden):
+    """the reference's do-while gives lookupN(key, 0)
+    one owner -- lookup(key)'s -- unless the key lies past the largest point,
+    where it gives []; the oracle and RingModel (and rp_ring_lookup_n_hashes:
+    test_gpu_ring_edges.py) give no owner on every key, and none for a
+    negative n, which the device refuses with RP_ERR_INVALID."""
+    g = golden("ring_edges.json")
+    assert 0 in g["ns"]
+    R = g["replica_points"]
+    probes = np.array(g["probes"], dtype=np.uint32)
+    m, orc = rc.RingModel(R), OracleRing(R)
+    rows_seen = {"one": 0, "past": 0, "empty": 0}
+    try:
+        for step in g["steps"]:
+            add, rm = step["add"], step["remove"]
+            ah = np.array([g["table"][s] for s in add], dtype=np.uint32).reshape(len(add), R)
+            rh = np.array([g["table"][s] for s in rm], dtype=np.uint32).reshape(len(rm), R)
+            m.add_remove(add, ah, rm, rh)
+            orc.add_remove(add, ah, rm, rh)
+            rows = step["lookupN"]["0"]
+            assert len(rows) == len(probes)
+            top = max((p[0] for p in step["points"]), default=None)
+            for x, row, owner in zip(probes.tolist(), rows, step["lookups"]):
+                for n in (0, -1):
+                    assert orc.lookup_n(x, n) == [] and m.lookup_n(x, n) == [], (x, n)
+                if top is None:
+                    assert row == [] and owner is None
+                    rows_seen["empty"] += 1
+                elif x > top:  # (lookup wraps to the first point; lookupN(key, 0) does not)
+                    assert row == [] and owner == step["points"][0][1], x
+                    rows_seen["past"] += 1
+                else:
+                    assert row == [owner] == step["lookupN"]["1"][probes.tolist().index(x)], x
+                    rows_seen["one"] += 1
+    finally:
+        orc.close()
+    assert all(rows_seen.values()), rows_seen
 
 
 # What each scenario is there for, as conditions on its inputs (from the
