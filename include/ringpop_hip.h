@@ -767,6 +767,69 @@ int rp_sim_route_n(rp_sim *sim, uint32_t replicas, const uint32_t *entries, cons
                    int32_t *dests, uint8_t *outcomes, uint8_t *holds, uint8_t *acks, rp_route_n_stats *stats);
 int rp_sim_route_n_uniform(rp_sim *sim, uint32_t replicas, uint64_t seed, uint64_t count, rp_route_n_stats *stats);
 
+/* ---- Multi-key requests (between rounds) ---------------------------------------
+ * rp_sim_route_all: what RingPop.handleOrProxyAll (index.js:636-694) meets
+ * across the cluster at one instant.  The batch is CSR:
+ * request i enters at node e = entries[i] with the key hashes
+ * key_hashes[offsets[i] .. offsets[i + 1]); offsets is [n + 1], non-decreasing,
+ * offsets[0] = 0, and a request has K = 0 .. 256 keys.  T = offsets[n].  The
+ * clock, liveness, partition window, ring checksums and "lookup in a view" are
+ * rp_sim_route's.
+ *   e fail-stopped or not yet joined: worst[i] = 4 ENTRY_DEAD, fanout[i] = 0,
+ *     every key of the request has key_group 0xFFFF and key_agrees 0, every
+ *     group slot is empty.
+ *   K = 0: fanout 0, worst 0 (index.js:648: the callback fires at once).
+ *   Otherwise e groups the keys by d = HashRing.lookup(h) in its own view (an
+ *     empty ring gives e): _.groupBy(keys, this.lookup) (index.js:640-645).
+ *     The groups are the distinct d in order of first appearance in the
+ *     request's key order; key_group[k] is the rank of key k's group and
+ *     fanout[i] the number of groups.  Group j of request i is stored at index
+ *     offsets[i] + j of the four group arrays (length T: a request never has
+ *     more groups than keys): group_dest = d, group_keys = its keys,
+ *     group_outcome = the first rule of rp_sim_route's table that applies to
+ *     (e, d) (0 LOCAL, 3 UNREACHABLE, 2 CHECKSUMS_DIFFER, 1 DELIVERED) and
+ *     group_agree = for outcome 1 or 2 the group's keys whose lookup in d's
+ *     own view is d, else 0.  Slots j >= fanout hold dest -1, outcome 255 and
+ *     counts 0.  key_agrees[k] = 1 iff the key's group has outcome 1 or 2 and
+ *     the key's lookup in d's view is d.  worst[i] is the largest group
+ *     outcome (0 < 1 < 2 < 3 by severity): with enforceConsistency, the
+ *     default, a request completes at once iff worst <= 1.
+ * The statistics count over live entries unless said otherwise: requests (all
+ * of the batch), entry_dead, empty (K = 0), keys, groups, groups and keys by
+ * (their group's) outcome, misrouted_keys (outcome 1 or 2 and key_agrees 0),
+ * split_groups (outcome 1 or 2 and 0 < group_agree < group_keys),
+ * worst_hist[worst], fanout_hist (bucket 0: fanout 0, else 1 + floor(log2
+ * fanout)) and max_fanout, the largest fanout of the batch.  Every output
+ * pointer may be NULL.
+ *
+ * rp_sim_route_all_uniform: the same for `count` requests of keys_per_request
+ * = K keys each (K in [1, 256]) drawn on the device: request i's entry is the
+ * entry of draw i * K of rp_sim_route_uniform's generator, its key j the key
+ * hash of draw i * K + j.  Only the statistics are returned.
+ *
+ * Exact, on the device, one launch per 2^31 keys; no census, no tracker and no
+ * cache is read or touched.  Both need every node's view on this process's
+ * device: RP_ERR_UNSUPPORTED on one rank of a multi-process or loop cluster;
+ * in-process shards give the one-shard result.  RP_ERR_INVALID, before any
+ * state changes, for a null sim, null entries, offsets or (T > 0) key_hashes
+ * with n > 0, an entry >= the cluster's size, offsets[0] != 0, decreasing
+ * offsets, a request of more than 256 keys or K outside [1, 256]; n == 0 does
+ * nothing. */
+typedef struct {
+    uint64_t requests, entry_dead, empty, keys, groups;
+    uint64_t group_outcome[4], key_outcome[4];
+    uint64_t misrouted_keys, split_groups;
+    uint64_t worst_hist[4], fanout_hist[10];
+    uint64_t max_fanout;
+    uint64_t reserved[2];
+} rp_route_all_stats;
+int rp_sim_route_all(rp_sim *sim, const uint32_t *entries, const uint64_t *offsets, const uint32_t *key_hashes, size_t n,
+                     uint16_t *key_group, uint8_t *key_agrees, int32_t *group_dest, uint8_t *group_outcome,
+                     uint16_t *group_keys, uint16_t *group_agree, uint16_t *fanout, uint8_t *worst,
+                     rp_route_all_stats *stats);
+int rp_sim_route_all_uniform(rp_sim *sim, uint64_t seed, uint64_t count, uint32_t keys_per_request,
+                             rp_route_all_stats *stats);
+
 /* ---- Request traffic with proxy retries across rounds ------------------------
  * Replaces the RequestProxySend state machine (lib/request-proxy/send.js) for
  * batches of single-key requests that live across rounds: a tracker keeps a

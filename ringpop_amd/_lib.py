@@ -87,6 +87,23 @@ class RouteNStats(ctypes.Structure):
         return d
 
 
+ROUTE_ALL_SCALARS_A = ("requests", "entry_dead", "empty", "keys", "groups")
+
+
+class RouteAllStats(ctypes.Structure):
+    _fields_ = ([(k, ctypes.c_uint64) for k in ROUTE_ALL_SCALARS_A] +
+                [("group_outcome", ctypes.c_uint64 * 4), ("key_outcome", ctypes.c_uint64 * 4),
+                 ("misrouted_keys", ctypes.c_uint64), ("split_groups", ctypes.c_uint64),
+                 ("worst_hist", ctypes.c_uint64 * 4), ("fanout_hist", ctypes.c_uint64 * 10),
+                 ("max_fanout", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 2)])
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in ROUTE_ALL_SCALARS_A + ("misrouted_keys", "split_groups", "max_fanout")}
+        for k in ("group_outcome", "key_outcome", "worst_hist", "fanout_hist"):
+            d[k] = [int(x) for x in getattr(self, k)]
+        return d
+
+
 MOVEMENT_SCALARS = ("same_set", "handed_off", "gained", "lost", "gainers", "losers", "max_gained", "max_gained_node",
                     "max_lost", "max_lost_node", "max_turnover", "max_turnover_hash", "from_clock", "to_clock", "intervals")
 
@@ -256,6 +273,9 @@ SIGNATURES = {
     "rp_sim_route_n": ([_P, ctypes.c_uint32, _P, _P, _SZ, _P, _P, _P, _P, ctypes.POINTER(RouteNStats)], ctypes.c_int),
     "rp_sim_route_n_uniform": ([_P, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(RouteNStats)],
                                ctypes.c_int),
+    "rp_sim_route_all": ([_P, _P, _P, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.POINTER(RouteAllStats)], ctypes.c_int),
+    "rp_sim_route_all_uniform": ([_P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(RouteAllStats)],
+                                 ctypes.c_int),
     "rp_ownership_snapshot_create": ([_P, ctypes.POINTER(_P)], ctypes.c_int),
     "rp_ownership_snapshot_info": ([_P, ctypes.POINTER(OwnershipStats), _U64P], ctypes.c_int),
     "rp_ownership_snapshot_destroy": ([_P], ctypes.c_int),

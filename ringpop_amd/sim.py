@@ -3,7 +3,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (MembershipStats, MovementStats, OwnershipStats, ReplicaMovementStats, ReplicationStats, RequestPending, RequestResult, RoundStats, RouteNStats, RouteStats, SimConfig, TrafficConfig, TrafficStats, check,
+from ._lib import (MembershipStats, MovementStats, OwnershipStats, ReplicaMovementStats, ReplicationStats, RequestPending, RequestResult, RoundStats, RouteAllStats, RouteNStats, RouteStats, SimConfig, TrafficConfig, TrafficStats, check,
                    lib, ptr)
 
 KERNEL_CATEGORIES = ("churn", "issue", "merge_ping", "merge_resp", "checksum", "other")
@@ -585,6 +585,45 @@ class Sim:
         st = RouteNStats()
         check(lib().rp_sim_route_n_uniform(self._h, int(replicas) & 0xFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF, int(count),
                                            ctypes.byref(st)))
+        return st.as_dict()
+
+    # ---- multi-key requests between rounds (rp_sim_route_all)
+    ROUTE_ALL_EMPTY = 255        # the outcome of a group slot past the request's groups
+    ROUTE_ALL_NO_GROUP = 0xFFFF  # the group of a dead entry's key
+
+    def route_all(self, entries, offsets, key_hashes):
+        """handleOrProxyAll at one instant: request i enters at node entries[i]
+        with the keys key_hashes[offsets[i]:offsets[i + 1]] (at most 256), the
+        entry groups them by owner in its own view and every group is one send.
+        A dict: per key `key_group` (uint16, the group's rank in order of first
+        appearance) and `key_agrees` (uint8); per group, request i's group j at
+        offsets[i] + j, `group_dest` (int32, -1 past the request's groups),
+        `group_outcome` (uint8, indices into ROUTE_OUTCOMES, ROUTE_ALL_EMPTY
+        past them), `group_keys` and `group_agree` (uint16); per request
+        `fanout` (uint16) and `worst` (uint8); `stats` (rp_route_all_stats)."""
+        e = np.ascontiguousarray(entries, dtype=np.uint32)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        h = np.ascontiguousarray(key_hashes, dtype=np.uint32)
+        if e.ndim != 1 or off.shape != (len(e) + 1,) or h.ndim != 1 or int(off[-1]) != len(h):
+            raise ValueError("route_all: entries [n], offsets [n + 1] ending at len(key_hashes)")
+        T = len(h)
+        out = {"key_group": np.zeros(T, dtype=np.uint16), "key_agrees": np.zeros(T, dtype=np.uint8),
+               "group_dest": np.zeros(T, dtype=np.int32), "group_outcome": np.zeros(T, dtype=np.uint8),
+               "group_keys": np.zeros(T, dtype=np.uint16), "group_agree": np.zeros(T, dtype=np.uint16),
+               "fanout": np.zeros(len(e), dtype=np.uint16), "worst": np.zeros(len(e), dtype=np.uint8)}
+        st = RouteAllStats()
+        check(lib().rp_sim_route_all(self._h, ptr(e), ptr(off), ptr(h), len(e), *(ptr(a) for a in out.values()),
+                                     ctypes.byref(st)))
+        out["stats"] = st.as_dict()
+        return out
+
+    def route_all_uniform(self, seed, count, keys_per_request):
+        """The stats of route_all() for `count` requests of `keys_per_request`
+        keys each, drawn on the device from splitmix64(seed)
+        (rp_sim_route_all_uniform)."""
+        st = RouteAllStats()
+        check(lib().rp_sim_route_all_uniform(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(count),
+                                             int(keys_per_request) & 0xFFFFFFFF, ctypes.byref(st)))
         return st.as_dict()
 
     # ---- ownership movement between two instants (rp_sim_ownership_moved; DESIGN.md §15)
