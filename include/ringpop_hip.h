@@ -390,9 +390,18 @@ int rp_sim_address(rp_sim *sim, uint32_t node, char *buf, size_t cap);
  * 96-105): farmhash32 of its servers' addresses, sorted and joined by ';'
  * (node ids are in address sort order).  out holds cap >= n entries; a
  * fail-stopped node reports its frozen ring, nodes of other processes' shards
- * report 0.  Computed on the device, one wave per view, and cached until a
- * call that can change a ring (round / run, update, handle_ping, set_views,
- * join, load_addresses).
+ * report 0.  Computed on the device and cached until a call that can change
+ * a ring (round / run, update, handle_ping, set_views, join, load_addresses).
+ * Each shard's views are hashed one view per wave or, for a shard of at least
+ * a threshold of views, one view per lane (64 views a wave):
+ * the same values either way.
+ *
+ * rp_sim_ring_checksum_lanes sets that threshold: 0 = the built-in value,
+ * 1 = always one view per lane, 0xFFFFFFFF = never (the meanings of
+ * rp_sim_config.ck_lane_min); it marks the cached checksums stale, so the
+ * next read recomputes on the chosen path.  rp_sim_ring_checksum_counts:
+ * out[0] = views handed to the wave kernel so far, out[1] = to the lane
+ * kernel (host counters, added at launch: a cached read adds nothing).
  *
  * rp_sim_route: what RingPop.handleOrProxy (index.js:607-634; lookup :409-423)
  * and the request proxy see for a batch of requests, request i entering the cluster
@@ -429,6 +438,8 @@ typedef struct {
     uint64_t requests, local, delivered, checksums_differ, unreachable, entry_dead, misrouted, reserved;
 } rp_route_stats;
 int rp_sim_ring_checksums(rp_sim *sim, uint32_t *out, size_t cap);
+int rp_sim_ring_checksum_lanes(rp_sim *sim, uint32_t lane_min);
+int rp_sim_ring_checksum_counts(rp_sim *sim, uint64_t out[2]);
 int rp_sim_route(rp_sim *sim, const uint32_t *entries, const uint32_t *key_hashes, size_t n, int32_t *dests,
                  uint8_t *outcomes, uint8_t *owner_agrees, rp_route_stats *stats);
 int rp_sim_route_uniform(rp_sim *sim, uint64_t seed, uint64_t count, rp_route_stats *stats);

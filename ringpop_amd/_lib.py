@@ -261,6 +261,8 @@ SIGNATURES = {
     "rp_sim_ring_lookup": ([_P, ctypes.c_uint32, _P, _SZ, _P], ctypes.c_int),
     "rp_sim_address": ([_P, ctypes.c_uint32, ctypes.c_char_p, _SZ], ctypes.c_int),
     "rp_sim_ring_checksums": ([_P, _P, _SZ], ctypes.c_int),
+    "rp_sim_ring_checksum_lanes": ([_P, ctypes.c_uint32], ctypes.c_int),
+    "rp_sim_ring_checksum_counts": ([_P, _U64P], ctypes.c_int),
     "rp_sim_route": ([_P, _P, _P, _SZ, _P, _P, _P, ctypes.POINTER(RouteStats)], ctypes.c_int),
     "rp_sim_route_uniform": ([_P, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(RouteStats)], ctypes.c_int),
     "rp_sim_ownership": ([_P, ctypes.POINTER(OwnershipStats), _P, _SZ], ctypes.c_int),

@@ -292,6 +292,10 @@ uint32_t loop_ranks(const rp_loop* group);
 // (every segment copy of a collective in launches of COPY_BATCH; dst[i] += src[i])
 void copy_batches(const std::vector<CopyDesc>& segs, hipStream_t st);
 void add_u32(uint32_t* dst, const uint32_t* src, size_t count, hipStream_t st);
+// rp_ringck.hip's launch: the ring checksums of views [lo, lo + nl), whose
+// in_ring rows (nl x n) start at in_ring, one view per lane, into out[lo ..]
+void launch_ring_checksums_pl(const uint8_t* in_ring, uint32_t n, uint32_t lo, uint32_t nl, const uint32_t* addr_words,
+                              const uint8_t* addr_len, uint32_t* out, hipStream_t st);
 
 }  // namespace rp
 
@@ -354,6 +358,14 @@ struct rp_sim {
     // hashes are built on first use and dropped with the shards
     // (rp_sim_load_addresses)
     bool ring_csum_stale = true;
+    // a shard of at least this many views has its ring checksums hashed one
+    // view per lane (k_ring_checksums_pl), a smaller one one view per wave
+    // (k_ring_checksums); rp_sim_ring_checksum_lanes sets it, 0 there = the
+    // measured default below.  Views launched on either path
+    // so far (host counters; a cached read adds nothing)
+    static constexpr uint32_t RING_CK_LANE_MIN = 65536;
+    uint32_t ring_ck_lane_min = RING_CK_LANE_MIN;
+    uint64_t ring_ck_views[2] = {0, 0};  // wave, lane
     // an entry point that can change a ring ran: both caches (this one and
     // the censuses') are stale
     void rings_changed() {

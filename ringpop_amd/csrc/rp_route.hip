@@ -278,10 +278,16 @@ void rp_sim::refresh_ring_checksums() {
             s.ring_csum.alloc(s.n);
             RP_HIP(hipMemsetAsync(s.ring_csum.p, 0, s.ring_csum.bytes(), s.st));
         }
+        const bool lanes = s.nl >= ring_ck_lane_min;
         s.timed(4, [&] {
-            hipLaunchKernelGGL(rp::k_ring_checksums, dim3(std::min(rp::grid_for(s.nl, rp::NWAVE), 8192u)), dim3(rp::BLOCK),
-                               0, s.st, s.d, s.ring_csum.p);
+            if (lanes)
+                rp::launch_ring_checksums_pl(s.d.in_ring, s.d.n, s.d.lo, s.d.nl, s.d.addr_words, s.d.addr_len,
+                                             s.ring_csum.p, s.st);
+            else
+                hipLaunchKernelGGL(rp::k_ring_checksums, dim3(std::min(rp::grid_for(s.nl, rp::NWAVE), 8192u)),
+                                   dim3(rp::BLOCK), 0, s.st, s.d, s.ring_csum.p);
         });
+        ring_ck_views[lanes ? 1 : 0] += s.nl;
         RP_HIP(hipGetLastError());
     }
     ring_csum_stale = false;
@@ -372,6 +378,22 @@ int rp_sim_ring_checksums(rp_sim* c, uint32_t* out, size_t cap) {
             RP_HIP(hipMemcpyAsync(out + s->lo, s->ring_csum.p + s->lo, (size_t)s->nl * 4, hipMemcpyDeviceToHost, s->st));
             RP_HIP(hipStreamSynchronize(s->st));
         }
+    });
+}
+
+int rp_sim_ring_checksum_lanes(rp_sim* c, uint32_t lane_min) {
+    return rp::guarded([&] {
+        if (!c) throw Error(RP_ERR_INVALID, "null pointer");
+        c->ring_ck_lane_min = lane_min ? lane_min : rp_sim::RING_CK_LANE_MIN;
+        c->ring_csum_stale = true;  // the next read recomputes, on the chosen path
+    });
+}
+
+int rp_sim_ring_checksum_counts(rp_sim* c, uint64_t out[2]) {
+    return rp::guarded([&] {
+        if (!c || !out) throw Error(RP_ERR_INVALID, "null pointer");
+        out[0] = c->ring_ck_views[0];
+        out[1] = c->ring_ck_views[1];
     });
 }
 

@@ -437,6 +437,20 @@ class Sim:
         check(lib().rp_sim_ring_checksums(self._h, ptr(out), len(out)))
         return out
 
+    def ring_checksum_lanes(self, lane_min):
+        """Shards of at least lane_min views have their ring checksums hashed
+        one view per lane, smaller ones one view per wave: 0 = the built-in
+        threshold, 1 = always per lane, 0xFFFFFFFF = never.  The next
+        ring_checksums() recomputes on the chosen path."""
+        check(lib().rp_sim_ring_checksum_lanes(self._h, int(lane_min)))
+
+    def ring_checksum_counts(self):
+        """Views handed so far to the wave and to the lane ring checksum
+        kernel (a cached read adds nothing)."""
+        out = (ctypes.c_uint64 * 2)()
+        check(lib().rp_sim_ring_checksum_counts(self._h, out))
+        return {"wave_views": int(out[0]), "lane_views": int(out[1])}
+
     def route(self, entries, key_hashes):
         """handleOrProxy for request i entering at node entries[i] with key hash
         key_hashes[i], with the next round's clock: (dests, outcomes (indices
