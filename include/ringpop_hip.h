@@ -952,6 +952,98 @@ int rp_traffic_times(rp_traffic *traffic, double *ms2, uint64_t *calls2, uint64_
  * at most the sum of the delays of its max_retries retries -- and a call that would need more fails with
  * RP_ERR_CAPACITY before any state changes. */
 
+/* ---- Multi-key request traffic across rounds ---------------------------------
+ * RingPop.handleOrProxyAll's requests through the request proxy's retry machine
+ * (DESIGN.md §23): a tracker of its own beside rp_traffic.  Everything not said
+ * here is rp_traffic's rules 1-5 above; the clock, liveness, the partition
+ * window, ring checksums and "lookup in a view" are rp_sim_route's.  A request
+ * is (entry e, keys h[0..K)), K = 0..256, and gets a 64-bit id in submission
+ * order.
+ *   Submission.  e fail-stopped or not yet joined: the request is final
+ *   ENTRY_DEAD, with no sends.  K = 0: final, no sends, ok.  Otherwise e groups
+ *   the keys exactly as rp_sim_route_all does (by lookup in e's own view, groups
+ *   in order of first appearance, keys of a group in input order); the number of
+ *   groups is the request's fanout.  Every group is one send with the group's
+ *   keys to the group's owner d: d == e: the send is final LOCAL; otherwise
+ *   proxied++, d0 = d and the send enters rule 2: send(e -> d0), error,
+ *   schedule.  On a success at destination d, misrouted_keys grows by the number
+ *   of the send's keys whose lookup in d's own view is not d.
+ *   Retry of a send (attemptRetry, send.js:105-127), at the first poll whose
+ *   clock is >= its due clock, in this order: (1) e fail-stopped: final
+ *   ENTRY_DEAD, nothing else counted; (2) retries++ (numRetries grows before
+ *   the lookup); (3) D = the distinct values of lookup(h) in e's view over the
+ *   send's keys (an empty ring gives e); (4) |D| > 1: aborted++, final ABORTED
+ *   with dest d0 (RetryDivergenceError, :105-113), nothing else counted; (5)
+ *   otherwise retry_attempted++ and nd = the one value, and from here it is rule
+ *   4 exactly: nd is compared with the original d0, retry_rerouted when they
+ *   differ, REROUTED_LOCAL when nd == e, else proxied++ and send(e -> nd).
+ *   Errors, max_retries, the schedule index, zero delays taken in the same call,
+ *   retry_succeeded and retry_failed are rules 2, 3 and 5.
+ *   Request level.  A request stays in the tracker until its last send is
+ *   final (the reference's other sends go on retrying after the callback has
+ *   fired with an error).  Its outcome is the largest send outcome; it is ok iff
+ *   that is <= 2.  first_error_clock is the clock of its first send to end with
+ *   an outcome >= 3 (0xFFFFFFFF if none, and for a request without sends);
+ *   done_clock is the clock at which its last send became final.
+ * rp_traffic_config is reused: max_retries, schedule, enforce_consistency,
+ * track, and capacity = the most pending requests (<= 2^26); timing is ignored.
+ * key_capacity = the most keys of pending requests (<= 2^31); 0 = 16 x
+ * capacity.  A call that could exceed either fails with RP_ERR_CAPACITY before
+ * any state changes; run presizes by rp_traffic_run's bound.
+ * RP_ERR_UNSUPPORTED on one rank of a multi-process or loop cluster;
+ * RP_ERR_INVALID as for rp_sim_route_all.  Destroy a tracker before its
+ * simulation. */
+typedef struct rp_traffic_all rp_traffic_all;
+#define RP_REQUEST_ABORTED 5
+typedef struct {
+    /* requests_ok + requests_failed: the requests that have left the tracker, by "outcome <= 2"; a request of a
+     * dead entry counts as failed, one without keys as ok.  keys, sends: of the requests of live entries */
+    uint64_t requests, requests_entry_dead, requests_empty, requests_ok, requests_failed;
+    uint64_t keys, sends;
+    uint64_t local, delivered, rerouted_local, failed, entry_dead, aborted; /* final sends by outcome */
+    uint64_t proxied, send_unreachable, checksums_differ, retry_scheduled, retry_attempted, retry_rerouted,
+        retry_succeeded, retry_failed, misrouted_keys;
+    uint64_t reserved[2];
+} rp_traffic_all_stats;
+typedef struct {
+    uint8_t outcome;          /* RP_REQUEST_*; 255 while a send is open */
+    uint8_t max_retries_seen; /* the largest retry count among its sends so far */
+    uint16_t fanout;
+    uint32_t submit_clock;
+    uint32_t first_error_clock;
+    uint32_t done_clock;      /* pending: 0 */
+} rp_request_all_result;
+typedef struct {
+    uint64_t id;
+    uint32_t entry;
+    uint16_t group, nkeys;    /* the send's group in its request, its keys */
+    int32_t first_dest;       /* d0 */
+    uint32_t due, submit_clock, retries;
+} rp_send_pending;
+int rp_traffic_all_create(rp_sim *sim, const rp_traffic_config *cfg, uint64_t key_capacity, rp_traffic_all **out);
+int rp_traffic_all_destroy(rp_traffic_all *traffic);
+/* n requests in rp_sim_route_all's CSR batch, with its argument rules, make their first sends now */
+int rp_traffic_all_submit(rp_traffic_all *traffic, const uint32_t *entries, const uint64_t *offsets,
+                          const uint32_t *key_hashes, size_t n, uint64_t *first_id);
+/* the same for requests first .. first + count - 1 of rp_sim_route_all_uniform's generator: request i takes the entry
+ * of draw i * K and the key hash of draw i * K + j */
+int rp_traffic_all_submit_uniform(rp_traffic_all *traffic, uint64_t seed, uint64_t first, uint64_t count,
+                                  uint32_t keys_per_request);
+/* every open send that is due retries */
+int rp_traffic_all_poll(rp_traffic_all *traffic);
+/* k times: a round, a poll, a submit_uniform that continues the index of earlier runs; no readback per round beyond
+ * rp_sim_round's error check */
+int rp_traffic_all_run(rp_traffic_all *traffic, int k_rounds, int churn_active, uint64_t per_round,
+                       uint32_t keys_per_request, uint64_t seed);
+/* cumulative statistics and by_retries[outcome * 9 + r]: final sends per outcome (6) and retry count r = 0..8 */
+int rp_traffic_all_read_stats(rp_traffic_all *traffic, rp_traffic_all_stats *cumulative, uint64_t *by_retries);
+/* the open sends by (id, group) and their keys concatenated; *nsends, *nkeys = the lengths; sends and keys may be
+ * NULL, else cap >= *nsends and key_cap >= *nkeys */
+int rp_traffic_all_pending(rp_traffic_all *traffic, rp_send_pending *sends, size_t cap, uint64_t *nsends,
+                           uint32_t *keys, size_t key_cap, uint64_t *nkeys);
+/* the records of requests first_id .. first_id + n - 1 (track only) */
+int rp_traffic_all_results(rp_traffic_all *traffic, uint64_t first_id, size_t n, rp_request_all_result *out);
+
 /* per-kernel device time (HIP events on the simulation stream), ms, summed
  * since enable; names: churn, issue(phase1), merge_ping(phase2),
  * merge_resp(phase3), checksum, other */

@@ -174,6 +174,30 @@ class RequestPending(ctypes.Structure):
                 ("retries", ctypes.c_uint32)]
 
 
+TRAFFIC_ALL_STATS = ("requests", "requests_entry_dead", "requests_empty", "requests_ok", "requests_failed", "keys", "sends",
+                     "local", "delivered", "rerouted_local", "failed", "entry_dead", "aborted", "proxied",
+                     "send_unreachable", "checksums_differ", "retry_scheduled", "retry_attempted", "retry_rerouted",
+                     "retry_succeeded", "retry_failed", "misrouted_keys")
+
+
+class TrafficAllStats(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint64) for k in TRAFFIC_ALL_STATS] + [("reserved", ctypes.c_uint64 * 2)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in TRAFFIC_ALL_STATS}
+
+
+class RequestAllResult(ctypes.Structure):
+    _fields_ = [("outcome", ctypes.c_uint8), ("max_retries_seen", ctypes.c_uint8), ("fanout", ctypes.c_uint16),
+                ("submit_clock", ctypes.c_uint32), ("first_error_clock", ctypes.c_uint32), ("done_clock", ctypes.c_uint32)]
+
+
+class SendPending(ctypes.Structure):
+    _fields_ = [("id", ctypes.c_uint64), ("entry", ctypes.c_uint32), ("group", ctypes.c_uint16), ("nkeys", ctypes.c_uint16),
+                ("first_dest", ctypes.c_int32), ("due", ctypes.c_uint32), ("submit_clock", ctypes.c_uint32),
+                ("retries", ctypes.c_uint32)]
+
+
 # (name, argtypes) of every entry point declared in include/ringpop_hip.h
 _P = ctypes.c_void_p
 _U8P = ctypes.POINTER(ctypes.c_uint8)
@@ -298,6 +322,15 @@ SIGNATURES = {
     "rp_traffic_pending": ([_P, _P, _SZ, _U64P], ctypes.c_int),
     "rp_traffic_results": ([_P, ctypes.c_uint64, _SZ, _P], ctypes.c_int),
     "rp_traffic_times": ([_P, _P, _P, _U64P], ctypes.c_int),
+    "rp_traffic_all_create": ([_P, ctypes.POINTER(TrafficConfig), ctypes.c_uint64, ctypes.POINTER(_P)], ctypes.c_int),
+    "rp_traffic_all_destroy": ([_P], ctypes.c_int),
+    "rp_traffic_all_submit": ([_P, _P, _P, _P, _SZ, _U64P], ctypes.c_int),
+    "rp_traffic_all_submit_uniform": ([_P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32], ctypes.c_int),
+    "rp_traffic_all_poll": ([_P], ctypes.c_int),
+    "rp_traffic_all_run": ([_P, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64], ctypes.c_int),
+    "rp_traffic_all_read_stats": ([_P, ctypes.POINTER(TrafficAllStats), _P], ctypes.c_int),
+    "rp_traffic_all_pending": ([_P, _P, _SZ, _U64P, _P, _SZ, _U64P], ctypes.c_int),
+    "rp_traffic_all_results": ([_P, ctypes.c_uint64, _SZ, _P], ctypes.c_int),
     "rp_sim_ping_body": ([_P, ctypes.c_uint32, _P, ctypes.c_uint32, _U32P, _U32P, ctypes.POINTER(ctypes.c_uint64)],
                          ctypes.c_int),
     "rp_sim_handle_ping": ([_P, ctypes.c_uint32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint32, _P, ctypes.c_uint32,

@@ -15,7 +15,7 @@ OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libringpop_hip.so")
 SOURCES = ["rp_capi.hip", "rp_ring.hip", "rp_sim.hip", "rp_route.hip", "rp_traffic.hip", "rp_own.hip", "rp_repl.hip", "rp_xport.hip",
            "rp_node.hip", "rp_calib.hip", "rp_hold.hip", "rp_routen.hip", "rp_rmove.hip", "rp_members.hip", "rp_routeall.hip",
-           "rp_ringck.hip"]
+           "rp_ringck.hip", "rp_trafficall.hip"]
 _INCLUDE_RE = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)
 
 
@@ -45,7 +45,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-Wall", "-Wno-
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {"rp_routen.hip": _NO_PACKED_FP32, "rp_rmove.hip": _NO_PACKED_FP32,
                 "rp_members.hip": _NO_PACKED_FP32, "rp_routeall.hip": _NO_PACKED_FP32,
-                "rp_ringck.hip": _NO_PACKED_FP32}
+                "rp_ringck.hip": _NO_PACKED_FP32, "rp_trafficall.hip": _NO_PACKED_FP32}
 # Builds of the same sources with other compile-time settings, each its own
 # library next to the product (loaded through RINGPOP_HIP_LIB):
 #  diag -- in-kernel cycle stamps (RP_DIAG);

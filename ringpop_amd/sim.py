@@ -3,7 +3,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (MembershipStats, MovementStats, OwnershipStats, ReplicaMovementStats, ReplicationStats, RequestPending, RequestResult, RoundStats, RouteAllStats, RouteNStats, RouteStats, SimConfig, TrafficConfig, TrafficStats, check,
+from ._lib import (MembershipStats, MovementStats, OwnershipStats, ReplicaMovementStats, ReplicationStats, RequestAllResult, RequestPending, RequestResult, RoundStats, RouteAllStats, RouteNStats, RouteStats, SendPending, SimConfig, TrafficAllStats, TrafficConfig, TrafficStats, check,
                    lib, ptr)
 
 KERNEL_CATEGORIES = ("churn", "issue", "merge_ping", "merge_resp", "checksum", "other")
@@ -125,6 +125,95 @@ class Traffic:
         check(lib().rp_traffic_times(self._h, ms, calls, ctypes.byref(peak)))
         return {"poll_ms": ms[0], "polls": int(calls[0]), "submit_ms": ms[1], "submits": int(calls[1]),
                 "peak_pending": int(peak.value)}
+
+
+class TrafficAll:
+    """rp_traffic_all: multi-key requests (handleOrProxyAll) with the request
+    proxy's retries and its abort on key divergence across rounds
+    (Sim.traffic_all).  Close it before the Sim (Sim.close does)."""
+
+    OUTCOMES = ("local", "delivered", "rerouted_local", "failed", "entry_dead", "aborted")
+    PENDING = 255
+    RESULT_DTYPE = np.dtype([("outcome", "u1"), ("max_retries_seen", "u1"), ("fanout", "<u2"), ("submit_clock", "<u4"),
+                             ("first_error_clock", "<u4"), ("done_clock", "<u4")])
+    SEND_DTYPE = np.dtype([("id", "<u8"), ("entry", "<u4"), ("group", "<u2"), ("nkeys", "<u2"), ("first_dest", "<i4"),
+                           ("due", "<u4"), ("submit_clock", "<u4"), ("retries", "<u4")])
+
+    def __init__(self, sim, max_retries=3, schedule=(0, 5, 18), enforce_consistency=True, track=False,
+                 capacity=1 << 20, key_capacity=0):
+        schedule = [int(x) for x in schedule]
+        if not 1 <= len(schedule) <= 8:
+            raise ValueError("traffic_all: a schedule of 1 to 8 delays")
+        if max_retries < 0:
+            raise ValueError("traffic_all: max_retries >= 0")
+        cfg = TrafficConfig(max_retries=int(max_retries), nschedule=len(schedule),
+                            enforce_consistency=1 if enforce_consistency else 0, track=1 if track else 0,
+                            capacity=int(capacity))
+        for i, x in enumerate(schedule):
+            cfg.schedule[i] = x
+        self._sim = sim
+        self._h = ctypes.c_void_p()
+        check(lib().rp_traffic_all_create(sim._h, ctypes.byref(cfg), int(key_capacity), ctypes.byref(self._h)))
+        sim._traffic.append(self)
+
+    def close(self):
+        if self._h:
+            lib().rp_traffic_all_destroy(self._h)
+            self._h = ctypes.c_void_p()
+            if self in self._sim._traffic:
+                self._sim._traffic.remove(self)
+
+    def submit(self, entries, offsets, key_hashes):
+        """First sends of request i = (entries[i], key_hashes[offsets[i]:offsets[i + 1]]) now (route_all's batch);
+        the id of request 0."""
+        e = np.ascontiguousarray(entries, dtype=np.uint32)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        h = np.ascontiguousarray(key_hashes, dtype=np.uint32)
+        if e.ndim != 1 or off.shape != (len(e) + 1,) or h.ndim != 1 or int(off[-1]) != len(h):
+            raise ValueError("submit: entries [n], offsets [n + 1] ending at len(key_hashes)")
+        first = ctypes.c_uint64(0)
+        check(lib().rp_traffic_all_submit(self._h, ptr(e), ptr(off), ptr(h) if len(h) else None, len(e),
+                                          ctypes.byref(first)))
+        return int(first.value)
+
+    def submit_uniform(self, seed, first, count, keys_per_request):
+        """Requests first .. first + count - 1 of route_all_uniform's generator, drawn on the device."""
+        check(lib().rp_traffic_all_submit_uniform(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), int(count),
+                                                  int(keys_per_request)))
+
+    def poll(self):
+        """Every open send that is due retries."""
+        check(lib().rp_traffic_all_poll(self._h))
+
+    def run(self, k, per_round, keys_per_request, seed, churn=True):
+        """k times: a round, a poll, a submit_uniform of per_round requests (rp_traffic_all_run)."""
+        check(lib().rp_traffic_all_run(self._h, int(k), 1 if churn else 0, int(per_round), int(keys_per_request),
+                                       int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def stats(self):
+        """(cumulative statistics, by_retries: {outcome: [final sends with 0..8 retries]})."""
+        st = TrafficAllStats()
+        by = np.zeros(54, dtype=np.uint64)
+        check(lib().rp_traffic_all_read_stats(self._h, ctypes.byref(st), ptr(by)))
+        return st.as_dict(), {k: by[9 * i:9 * i + 9].astype(np.int64).tolist() for i, k in enumerate(self.OUTCOMES)}
+
+    def pending(self):
+        """The open sends by (id, group) (a SEND_DTYPE array) and their keys, concatenated."""
+        assert self.SEND_DTYPE.itemsize == ctypes.sizeof(SendPending)
+        ns, nk = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        check(lib().rp_traffic_all_pending(self._h, None, 0, ctypes.byref(ns), None, 0, ctypes.byref(nk)))
+        sends = np.zeros(int(ns.value), dtype=self.SEND_DTYPE)
+        keys = np.zeros(int(nk.value), dtype=np.uint32)
+        check(lib().rp_traffic_all_pending(self._h, ptr(sends) if len(sends) else None, len(sends), ctypes.byref(ns),
+                                           ptr(keys) if len(keys) else None, len(keys), ctypes.byref(nk)))
+        return sends, keys
+
+    def results(self, first_id, n):
+        """The records of requests first_id .. first_id + n - 1 (track=True; a RESULT_DTYPE array)."""
+        assert self.RESULT_DTYPE.itemsize == ctypes.sizeof(RequestAllResult)
+        out = np.zeros(int(n), dtype=self.RESULT_DTYPE)
+        check(lib().rp_traffic_all_results(self._h, int(first_id), len(out), ptr(out) if len(out) else None))
+        return out
 
 
 class OwnershipSnapshot:
@@ -708,6 +797,11 @@ class Sim:
         schedule=(0, 5, 18) rounds, enforce_consistency=True, track=False,
         capacity=2**20, timing=False."""
         return Traffic(self, **cfg)
+
+    def traffic_all(self, **cfg):
+        """A multi-key request tracker on this simulation (rp_traffic_all_create):
+        traffic()'s keywords without timing, and key_capacity=0 (16 x capacity)."""
+        return TrafficAll(self, **cfg)
 
     def address(self, v):
         buf = ctypes.create_string_buffer(64)
